@@ -13,6 +13,11 @@ Usage:
   python bench.py --gpus 1 --steps 20 --warmup 5          # single GPU
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
       --master-addr 127.0.0.1 bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR
+      # + DIR/loss.npy, DIR/master_weights_sample.npy from the last step
+
+A plain run sets up, warms up, times the steps and prints the result line;
+--full is where any secondary measurement belongs (none exist today).
 
 Synthetic data (random tokens, fixed seed per step), random-init weights.
 Rank 0 prints ONE JSON line with the whole-job aggregate.
@@ -56,6 +61,34 @@ def build_model_cfg(model_name: str):
     raise ValueError(model_name)
 
 
+DUMP_SAMPLE_PER_UNIT = 1 << 18  # fp32 elements sampled per shard unit (1 MiB)
+DUMP_SAMPLE_MAX_TOTAL = 1 << 23  # whole dump stays under 32 MiB
+
+
+@torch.no_grad()
+def dump_outputs(out_dir: str, loss: torch.Tensor, sharded) -> None:
+    """Write what the last timed step handed back: its loss, and the state
+    it left behind — this rank's fp32 master weights, one fixed seeded
+    sample of DUMP_SAMPLE_PER_UNIT elements per shard unit (the full 2.7B
+    state is ~11 GB). Same arguments => same inputs => comparable files."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "loss.npy"),
+            loss.detach().float().reshape(1).cpu().numpy())
+    g = torch.Generator().manual_seed(4321)
+    per_unit = min(DUMP_SAMPLE_PER_UNIT,
+                   DUMP_SAMPLE_MAX_TOTAL // max(len(sharded.units), 1))
+    samples = []
+    for u in sharded.units:
+        shard = u.master_shard
+        if shard.numel() > per_unit:
+            idx = torch.randint(0, shard.numel(), (per_unit,), generator=g)
+            shard = shard[idx.to(shard.device)]
+        samples.append(shard.float().cpu())
+    np.save(os.path.join(out_dir, "master_weights_sample.npy"),
+            torch.cat(samples).numpy())
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--gpus", type=int, default=1)
@@ -75,7 +108,16 @@ def main():
     p.add_argument("--tp", type=int, default=1, help="tensor-parallel degree")
     p.add_argument("--no-graph", action="store_true",
                    help="disable hipGraph step capture")
+    p.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                   help="after the timed steps write what the last timed "
+                        "step computed (loss + a seeded sample of the "
+                        "updated fp32 master weights) as DIR/<name>.npy")
+    p.add_argument("--full", action="store_true",
+                   help="also run the benchmark's secondary measurements "
+                        "(none today: a plain run already does only what "
+                        "the headline figure needs)")
     args = p.parse_args()
+    assert args.steps >= 1, "--steps must be >= 1"
 
     rank = int(os.environ.get("RANK", 0))
     world = int(os.environ.get("WORLD_SIZE", 1))
@@ -241,7 +283,7 @@ def main():
         dist.barrier()
     t0 = time.perf_counter()
     for s in range(args.steps):
-        one_step(args.warmup + s)
+        last_loss = one_step(args.warmup + s)
     if on_gpu:
         torch.cuda.synchronize()
     if world > 1:
@@ -253,6 +295,9 @@ def main():
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = t.item()
+
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last_loss, sharded)
 
     ms_per_step = elapsed / args.steps * 1000
     tokens_per_step_global = B * T * dp_world

@@ -89,7 +89,8 @@ def test_bench_contract_multirank_cpu(tmp_path):
 
     from tests.conftest import find_free_port
     env = dict(os.environ)
-    env.pop("CUDA_VISIBLE_DEVICES", None)
+    # CPU/gloo on every host: hide any GPU from the two ranks
+    env["CUDA_VISIBLE_DEVICES"] = env["HIP_VISIBLE_DEVICES"] = ""
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run(
         [sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
@@ -118,3 +119,43 @@ def test_bench_contract_multirank_cpu(tmp_path):
     for field in ("model", "global_batch", "micro_batch", "seq_len",
                   "parallelism", "num_params"):
         assert field in d["config"], field
+
+
+def test_bench_dump_outputs_reproducible_cpu(tmp_path):
+    """--dump-outputs writes the last timed step's loss and a seeded sample
+    of the updated master weights as float32 .npy files; the same arguments
+    give the same files (same inputs), and --full is accepted."""
+    import os
+    import subprocess
+    import sys
+
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
+        env.pop(k, None)
+    # a CPU run wherever the suite runs: bit-identical across processes
+    env["CUDA_VISIBLE_DEVICES"] = env["HIP_VISIBLE_DEVICES"] = ""
+
+    def run(out_dir, *extra):
+        r = subprocess.run(
+            [sys.executable, os.path.join(repo, "bench.py"), "--gpus", "1",
+             "--steps", "2", "--warmup", "1", "--model", "gpt2-tiny",
+             "--micro-batch", "1", "--seq-len", "64", "--no-graph",
+             "--dump-outputs", str(out_dir), *extra],
+            capture_output=True, text=True, timeout=600, env=env, cwd=repo)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, r.stdout
+        d = json.loads(lines[0])
+        assert d["steps"] == 2 and d["ms_per_step"] > 0
+        return {f.name: np.load(f) for f in sorted(Path(out_dir).iterdir())}
+
+    a = run(tmp_path / "a")
+    b = run(tmp_path / "b", "--full")
+    assert sorted(a) == ["loss.npy", "master_weights_sample.npy"]
+    assert sorted(b) == sorted(a)
+    assert sum(v.nbytes for v in a.values()) <= 64 * 2**20
+    for name in a:
+        assert a[name].dtype == np.float32 and np.isfinite(a[name]).all()
+        np.testing.assert_array_equal(a[name], b[name])
+    assert a["loss.npy"].shape == (1,) and a["loss.npy"][0] > 0

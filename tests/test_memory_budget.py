@@ -63,6 +63,8 @@ def test_bench_world8_gloo_dry_run():
     env = dict(os.environ)
     env["MASTER_ADDR"] = "127.0.0.1"
     env.pop("RANK", None), env.pop("WORLD_SIZE", None)
+    # a CPU/gloo dry run on every host: hide any GPU from the eight ranks
+    env["CUDA_VISIBLE_DEVICES"] = env["HIP_VISIBLE_DEVICES"] = ""
     r = subprocess.run(
         [sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
          "--nproc-per-node", "8", "--master-addr", "127.0.0.1",
