@@ -38,6 +38,15 @@ __global__ void adamw_masked_kernel(float* __restrict__ p,
   }
 }
 
+// 1 - beta^t to a few fp32 ulps. 1.0f - __powf(beta, t) loses it twice: the
+// fast pow is only accurate to ~1e-6 near 1, and beta^t itself cannot be
+// held in fp32 to better than 2^-25 absolute, which is a relative error of
+// 2^-25 * beta^t / (1 - beta^t) in the result (1.5e-5 at beta2 = 0.999,
+// t = 2). -expm1(t * log(beta)) never forms beta^t. Once per thread.
+__device__ __forceinline__ float bias_correction(float beta, float t) {
+  return -expm1f(t * logf(beta));
+}
+
 // Graph-safe variant: the Adam step count lives in DEVICE memory so a
 // hipGraph replay of the training step sees the advancing bias correction
 // (a host-side bc baked into kernel args would be frozen at capture).
@@ -58,8 +67,8 @@ __global__ void adamw_masked_devstep_kernel(float* __restrict__ p,
   // over every grad shard that multi_tensor_scale_ would cost.
   const float gs = gscale ? *gscale : 1.0f;
   const float t = (float)*step;
-  const float bc1 = 1.0f - __powf(beta1, t);
-  const float bc2 = 1.0f - __powf(beta2, t);
+  const float bc1 = bias_correction(beta1, t);
+  const float bc2 = bias_correction(beta2, t);
   const float step_size = lr / bc1;
   const float inv_bc2 = 1.0f / bc2;
   floatx4* p4 = reinterpret_cast<floatx4*>(p);
@@ -98,8 +107,8 @@ __global__ void adamw_devstep_wide_kernel(float* __restrict__ p,
                                           float beta2, float eps, float wd) {
   const float gs = gscale ? *gscale : 1.0f;
   const float t = (float)*step;
-  const float bc1 = 1.0f - __powf(beta1, t);
-  const float bc2 = 1.0f - __powf(beta2, t);
+  const float bc1 = bias_correction(beta1, t);
+  const float bc2 = bias_correction(beta2, t);
   const float step_size = lr / bc1;
   const float inv_bc2 = 1.0f / bc2;
   floatx4* p4 = reinterpret_cast<floatx4*>(p);
@@ -172,6 +181,12 @@ int grid_for(long work, int block) {
   return (int)min(g, (long)(256 * 8));
 }
 
+// t is a contiguous device fp32 tensor with as many elements as ref
+bool f32_like(const torch::Tensor& t, const torch::Tensor& ref) {
+  return t.is_cuda() && t.dtype() == torch::kFloat32 && t.is_contiguous()
+      && t.numel() == ref.numel() && t.device() == ref.device();
+}
+
 }  // namespace
 
 void fused_adamw_masked(torch::Tensor p, torch::Tensor g, torch::Tensor m,
@@ -180,6 +195,9 @@ void fused_adamw_masked(torch::Tensor p, torch::Tensor g, torch::Tensor m,
                         double bc1, double bc2) {
   TORCH_CHECK(p.is_cuda() && p.dtype() == torch::kFloat32 && p.is_contiguous());
   TORCH_CHECK(p.numel() % 4 == 0, "flat shard must be divisible by 4");
+  TORCH_CHECK(f32_like(g, p) && f32_like(m, p) && f32_like(v, p)
+              && f32_like(wd_mask, p),
+              "g, m, v, wd_mask must match p (device fp32, contiguous)");
   long n4 = p.numel() / 4;
   auto stream = at::cuda::getCurrentHIPStream();
   hipLaunchKernelGGL(adamw_masked_kernel, dim3(grid_for(n4, 256)), dim3(256), 0,
@@ -205,9 +223,13 @@ void fused_adamw_masked_devstep(torch::Tensor p, torch::Tensor g,
   }
   TORCH_CHECK(p.is_cuda() && p.dtype() == torch::kFloat32 && p.is_contiguous());
   TORCH_CHECK(p.numel() % 4 == 0, "flat shard must be divisible by 4");
-  TORCH_CHECK(step.is_cuda() && step.dtype() == torch::kInt32);
-  TORCH_CHECK(bf16_out.dtype() == torch::kBFloat16
-              && bf16_out.numel() == p.numel());
+  TORCH_CHECK(f32_like(g, p) && f32_like(m, p) && f32_like(v, p)
+              && f32_like(wd_mask, p),
+              "g, m, v, wd_mask must match p (device fp32, contiguous)");
+  TORCH_CHECK(step.is_cuda() && step.dtype() == torch::kInt32
+              && step.numel() == 1);
+  TORCH_CHECK(bf16_out.is_cuda() && bf16_out.dtype() == torch::kBFloat16
+              && bf16_out.is_contiguous() && bf16_out.numel() == p.numel());
   long n4 = p.numel() / 4;
   auto stream = at::cuda::getCurrentHIPStream();
   static const int wide = []() {
@@ -252,6 +274,8 @@ void fused_adamw(std::vector<torch::Tensor> ps, std::vector<torch::Tensor> gs,
                  std::vector<torch::Tensor> ms, std::vector<torch::Tensor> vs,
                  double lr, double beta1, double beta2, double eps, double wd,
                  double bc1, double bc2) {
+  TORCH_CHECK(gs.size() == ps.size() && ms.size() == ps.size()
+              && vs.size() == ps.size(), "fused_adamw: list lengths differ");
   for (size_t i = 0; i < ps.size(); ++i) {
     auto ones = torch::ones_like(ps[i]);
     fused_adamw_masked(ps[i], gs[i], ms[i], vs[i], ones, lr, beta1, beta2, eps,
@@ -264,8 +288,8 @@ torch::Tensor multi_tensor_sqsum(std::vector<torch::Tensor> tensors) {
   auto out = torch::zeros({}, tensors[0].options().dtype(torch::kFloat32));
   auto stream = at::cuda::getCurrentHIPStream();
   for (auto& t : tensors) {
-    TORCH_CHECK(t.dtype() == torch::kFloat32 && t.is_contiguous()
-                && t.numel() % 4 == 0);
+    TORCH_CHECK(t.is_cuda() && t.dtype() == torch::kFloat32
+                && t.is_contiguous() && t.numel() % 4 == 0);
     long n4 = t.numel() / 4;
     hipLaunchKernelGGL(sqsum_kernel, dim3(grid_for(n4, 256)), dim3(256), 0,
                        stream, t.data_ptr<float>(), n4, out.data_ptr<float>());
@@ -275,8 +299,19 @@ torch::Tensor multi_tensor_sqsum(std::vector<torch::Tensor> tensors) {
 }
 
 void multi_tensor_scale(std::vector<torch::Tensor> tensors, torch::Tensor scale) {
+  // scale stays on device (hipGraph-capture-safe): a host scalar is an error
+  TORCH_CHECK(scale.is_cuda() && scale.numel() == 1,
+              "multi_tensor_scale: scale must be a device scalar");
+  // a tail of numel % 4 elements would be left unscaled: reject, like
+  // multi_tensor_sqsum and the AdamW kernels (shards are padded). All
+  // tensors are validated before the first launch.
+  for (auto& t : tensors)
+    TORCH_CHECK(t.is_cuda() && t.dtype() == torch::kFloat32
+                && t.is_contiguous() && t.numel() % 4 == 0,
+                "multi_tensor_scale: tensors must be contiguous device fp32 "
+                "with numel % 4 == 0");
   auto stream = at::cuda::getCurrentHIPStream();
-  auto s = scale.to(torch::kFloat32);
+  auto s = scale.to(torch::kFloat32).contiguous();
   for (auto& t : tensors) {
     long n4 = t.numel() / 4;
     hipLaunchKernelGGL(scale_kernel, dim3(grid_for(n4, 256)), dim3(256), 0,

@@ -1121,6 +1121,28 @@ __global__ void delta2_kernel(const unsigned short* __restrict__ dout,
 
 }  // namespace attn2
 
+// k: contiguous device bf16 [B,Tkv,Hkv,D] matching q's B and D. v: the same
+// shape, contiguous or a row-strided view (strides (Tkv*vp, vp, D, 1)); the
+// kernels read V rows with 16-byte loads, so vp and the storage offset must
+// keep them 16-byte aligned.
+static bool attn2_kv_ok(const torch::Tensor& q, const torch::Tensor& k,
+                        const torch::Tensor& v) {
+  if (q.dim() != 4 || k.dim() != 4 || v.dim() != 4) return false;
+  const long B = q.size(0), D = q.size(3);
+  if (!(k.is_cuda() && k.device() == q.device()
+        && k.dtype() == torch::kBFloat16 && k.is_contiguous()
+        && k.size(0) == B && k.size(3) == D && k.size(1) >= 1
+        && k.size(2) >= 1))
+    return false;
+  const long Tkv = k.size(1);
+  return v.is_cuda() && v.device() == q.device()
+      && v.dtype() == torch::kBFloat16 && v.sizes() == k.sizes()
+      && v.stride(3) == 1 && v.stride(2) == D
+      && v.stride(1) >= k.size(2) * D && v.stride(1) % 8 == 0
+      && v.storage_offset() % 8 == 0
+      && (B == 1 || v.stride(0) == Tkv * v.stride(1));
+}
+
 // ---------------------------------------------------------------------------
 std::vector<torch::Tensor> attn_fwd2(torch::Tensor q, torch::Tensor k,
                                      torch::Tensor v, bool causal,
@@ -1132,10 +1154,10 @@ std::vector<torch::Tensor> attn_fwd2(torch::Tensor q, torch::Tensor k,
   const int Tkv = k.size(1), Hkv = k.size(2);
   // V may be a row-strided view into the joint QKV activation (the fused
   // path reads it in place): strides must be (Tkv*vp, vp, D, 1).
-  TORCH_CHECK(k.is_contiguous());
-  TORCH_CHECK(v.stride(3) == 1 && v.stride(2) == D
-              && (B == 1 || v.stride(0) == (long)Tkv * v.stride(1)),
-              "v must be contiguous or a [B,T,Hkv,D] view with row stride");
+  TORCH_CHECK(attn2_kv_ok(q, k, v), "k must be contiguous device bf16 "
+              "[B,Tkv,Hkv,D]; v the same or a [B,Tkv,Hkv,D] view with a row "
+              "stride that is a multiple of 8");
+  TORCH_CHECK(q_offset >= 0, "attn_fwd2: q_offset must be >= 0");
   // (B == 1: the batch-stride term is never used, so a dim-1 slice of a
   // longer KV-cache buffer is read in place — zero-copy decode)
   const long vp = v.stride(1);
@@ -1168,12 +1190,31 @@ static std::vector<torch::Tensor> attn_bwd2_impl(
     torch::Tensor o, torch::Tensor lse, bool causal, long q_offset,
     torch::Tensor dv, long dvp, long dvc) {
   TORCH_CHECK(causal, "attn_bwd2: only causal attention is implemented");
-  TORCH_CHECK(q.is_cuda() && q.dtype() == torch::kBFloat16 && q.is_contiguous());
+  TORCH_CHECK(q.is_cuda() && q.dtype() == torch::kBFloat16 && q.dim() == 4
+              && q.is_contiguous(), "q must be contiguous bf16 [B,T,Hq,D]");
   const int B = q.size(0), T = q.size(1), Hq = q.size(2), D = q.size(3);
+  TORCH_CHECK(attn2_kv_ok(q, k, v), "k must be contiguous device bf16 "
+              "[B,Tkv,Hkv,D]; v the same or a [B,Tkv,Hkv,D] view with a row "
+              "stride that is a multiple of 8");
   const int Tkv = k.size(1), Hkv = k.size(2);
-  TORCH_CHECK(v.stride(3) == 1 && v.stride(2) == D
-              && (B == 1 || v.stride(0) == (long)Tkv * v.stride(1)),
-              "v must be contiguous or a [B,T,Hkv,D] view with row stride");
+  TORCH_CHECK(Hq % Hkv == 0, "GQA requires Hq % Hkv == 0");
+  TORCH_CHECK(q_offset >= 0, "attn_bwd2: q_offset must be >= 0");
+  auto same_as_q = [&](const torch::Tensor& t) {
+    return t.is_cuda() && t.device() == q.device()
+        && t.dtype() == torch::kBFloat16 && t.is_contiguous()
+        && t.sizes() == q.sizes();
+  };
+  TORCH_CHECK(same_as_q(dout) && same_as_q(o),
+              "dout and o must be contiguous device bf16 shaped like q");
+  TORCH_CHECK(lse.is_cuda() && lse.device() == q.device()
+              && lse.dtype() == torch::kFloat32 && lse.is_contiguous()
+              && lse.dim() == 3 && lse.size(0) == B && lse.size(1) == Hq
+              && lse.size(2) == T, "lse must be contiguous fp32 [B,Hq,T]");
+  TORCH_CHECK(dv.is_cuda() && dv.device() == q.device()
+              && dv.dtype() == torch::kBFloat16 && dv.is_contiguous()
+              && dvc >= 0 && dvc + (long)Hkv * D <= dvp
+              && dv.numel() == (long)B * Tkv * dvp,
+              "dv target must be contiguous device bf16 [B,Tkv,pitch]");
   // (B == 1: the batch-stride term is never used, so a dim-1 slice of a
   // longer KV-cache buffer is read in place — zero-copy decode)
   const long vstride = v.stride(1);

@@ -22,13 +22,14 @@ __device__ __forceinline__ float bf16_to_f32(unsigned short u) {
 }
 
 __device__ __forceinline__ unsigned short f32_to_bf16(float f) {
-  union { float f; unsigned int i; } c;
-  c.f = f;
-  unsigned int i = c.i;
-  // round-to-nearest-even
-  unsigned int rounded = i + 0x7FFF + ((i >> 16) & 1);
-  if ((i & 0x7F800000) == 0x7F800000) rounded = i;  // inf/nan passthrough
-  return (unsigned short)(rounded >> 16);
+  // The hardware convert (v_cvt_pk_bf16_f32; hipcc pairs adjacent casts)
+  // rounds to nearest even and keeps every NaN a NaN. The bit-twiddled
+  // form it replaces truncated a NaN whose payload lies in the low 16 bits
+  // to Inf, and cost ~6 VALU per element, which the elementwise kernels
+  // cannot hide (silu*mul sits at its issue budget).
+  union { __bf16 h; unsigned short u; } c;
+  c.h = (__bf16)f;
+  return c.u;
 }
 
 // Wave-wide f32 sum via shuffle tree (64 lanes).

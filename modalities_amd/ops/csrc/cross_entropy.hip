@@ -23,25 +23,32 @@ __global__ void ce_fwd_kernel(const unsigned short* __restrict__ logits,
   const unsigned short* lr = logits + row * (long)V;
 
   float m = -INFINITY, s = 0.f;
-  const int vecV = V / 8;
+  // 16-byte vector loads need 16-byte aligned rows: only when V % 8 == 0
+  // (block-uniform branch); otherwise the scalar loop covers the whole row.
+  const int vecV = (V % 8 == 0) ? V / 8 : 0;
   const shortx8* lv = reinterpret_cast<const shortx8*>(lr);
+  // -inf logits (masked vocabulary entries) contribute exp(-inf) = 0 and
+  // are skipped: as a thread's first element they would give
+  // exp(-inf - (-inf)) = NaN.
   for (int i = threadIdx.x; i < vecV; i += BLOCK) {
     shortx8 v = lv[i];
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       float f = bf16_to_f32((unsigned short)v[j]);
+      if (f == -INFINITY) continue;
       if (f > m) { s *= __expf(m - f); m = f; }
       s += __expf(f - m);
     }
   }
   for (int i = vecV * 8 + threadIdx.x; i < V; i += BLOCK) {
     float f = bf16_to_f32(lr[i]);
+    if (f == -INFINITY) continue;
     if (f > m) { s *= __expf(m - f); m = f; }
     s += __expf(f - m);
   }
   // combine per-thread (m, s) pairs: block max then rescaled sums
   float bm = block_reduce_max(m, scratch);
-  s *= __expf(m - bm);
+  s = (m == -INFINITY) ? 0.f : s * __expf(m - bm);
   float bs = block_reduce_sum(s, scratch);
   const float lse = bm + __logf(bs);
   if (threadIdx.x == 0) {
@@ -66,7 +73,7 @@ __global__ void ce_bwd_kernel(const unsigned short* __restrict__ logits,
   const float l = lse[row];
   const bool ignored = (tgt == ignore_index);
 
-  const int vecV = V / 8;
+  const int vecV = (V % 8 == 0) ? V / 8 : 0;  // see ce_fwd_kernel
   const shortx8* lv = reinterpret_cast<const shortx8*>(lr);
   shortx8* dv = reinterpret_cast<shortx8*>(dr);
   for (int i = threadIdx.x; i < vecV; i += BLOCK) {
@@ -95,7 +102,10 @@ std::vector<torch::Tensor> cross_entropy_fwd(torch::Tensor logits,
                                              long ignore_index) {
   TORCH_CHECK(logits.is_cuda() && logits.dtype() == torch::kBFloat16
               && logits.dim() == 2 && logits.is_contiguous());
-  TORCH_CHECK(targets.dtype() == torch::kInt64 && targets.is_contiguous());
+  TORCH_CHECK(targets.is_cuda() && targets.dtype() == torch::kInt64
+              && targets.is_contiguous()
+              && targets.numel() == logits.size(0),
+              "cross_entropy_fwd: targets must be device int64 [N]");
   const long N = logits.size(0);
   const int V = logits.size(1);
   auto losses = torch::empty({N}, logits.options().dtype(torch::kFloat32));
@@ -112,8 +122,19 @@ std::vector<torch::Tensor> cross_entropy_fwd(torch::Tensor logits,
 torch::Tensor cross_entropy_bwd(torch::Tensor logits, torch::Tensor targets,
                                 torch::Tensor lse, torch::Tensor scale,
                                 long ignore_index) {
+  TORCH_CHECK(logits.is_cuda() && logits.dtype() == torch::kBFloat16
+              && logits.dim() == 2 && logits.is_contiguous(),
+              "cross_entropy_bwd: logits must be contiguous device bf16 [N,V]");
   const long N = logits.size(0);
   const int V = logits.size(1);
+  TORCH_CHECK(targets.is_cuda() && targets.dtype() == torch::kInt64
+              && targets.is_contiguous() && targets.numel() == N,
+              "cross_entropy_bwd: targets must be device int64 [N]");
+  TORCH_CHECK(lse.is_cuda() && lse.dtype() == torch::kFloat32
+              && lse.is_contiguous() && lse.numel() == N,
+              "cross_entropy_bwd: lse must be device fp32 [N]");
+  TORCH_CHECK(scale.is_cuda() && scale.numel() == 1,
+              "cross_entropy_bwd: scale must be a device scalar");
   auto dlogits = torch::empty_like(logits);
   // scale stays on device (a .item() here is a host sync that would break
   // hipGraph capture of the training step)

@@ -173,6 +173,18 @@ int grid_for(long work, int block) {
   return (int)min(g, (long)(256 * 8));  // cap + grid-stride (guide G11)
 }
 
+// t is a contiguous device fp32 [>= T, D/2] cos or sin table
+bool rope_table_ok(const torch::Tensor& t, long T, long D) {
+  return t.is_cuda() && t.dtype() == torch::kFloat32 && t.dim() == 2
+      && t.is_contiguous() && t.size(0) >= T && t.size(1) == D / 2;
+}
+
+// t is a contiguous device bf16 tensor with as many elements as ref
+bool bf16_like(const torch::Tensor& t, const torch::Tensor& ref) {
+  return t.is_cuda() && t.dtype() == torch::kBFloat16 && t.is_contiguous()
+      && t.numel() == ref.numel() && t.device() == ref.device();
+}
+
 }  // namespace
 
 torch::Tensor rope_fwd(torch::Tensor x, torch::Tensor cos_t, torch::Tensor sin_t,
@@ -181,8 +193,9 @@ torch::Tensor rope_fwd(torch::Tensor x, torch::Tensor cos_t, torch::Tensor sin_t
               && x.is_contiguous(), "rope: x must be contiguous bf16 [B,T,H,D]");
   const int B = x.size(0), T = x.size(1), Hn = x.size(2), D = x.size(3);
   TORCH_CHECK(D % 4 == 0, "rope: head_dim must be divisible by 4");
-  TORCH_CHECK(T <= 65535 && cos_t.size(0) >= T && cos_t.size(1) == D / 2);
-  TORCH_CHECK(cos_t.dtype() == torch::kFloat32 && cos_t.is_contiguous());
+  TORCH_CHECK(T <= 65535 && rope_table_ok(cos_t, T, D)
+              && rope_table_ok(sin_t, T, D),
+              "rope: cos/sin must be contiguous device fp32 [>=T, D/2]");
   auto out = torch::empty_like(x);
   auto stream = at::cuda::getCurrentHIPStream();
   const int work = Hn * (D / 4);
@@ -204,9 +217,11 @@ torch::Tensor rope_fwd_slice(torch::Tensor qkv, torch::Tensor cos_t,
               && qkv.dim() == 3 && qkv.is_contiguous());
   const int B = qkv.size(0), T = qkv.size(1);
   const long Ctot = qkv.size(2);
-  TORCH_CHECK(col_off % 2 == 0 && (D % 4) == 0 && col_off + Hn * D <= Ctot);
-  TORCH_CHECK(T <= 65535 && cos_t.size(0) >= T && cos_t.size(1) == D / 2
-              && cos_t.dtype() == torch::kFloat32 && cos_t.is_contiguous());
+  TORCH_CHECK(col_off >= 0 && col_off % 2 == 0 && Ctot % 2 == 0
+              && (D % 4) == 0 && col_off + Hn * D <= Ctot);
+  TORCH_CHECK(T <= 65535 && rope_table_ok(cos_t, T, D)
+              && rope_table_ok(sin_t, T, D),
+              "rope: cos/sin must be contiguous device fp32 [>=T, D/2]");
   auto out = torch::empty({B, T, Hn, D}, qkv.options());
   auto stream = at::cuda::getCurrentHIPStream();
   const int work = (int)(Hn * (D / 4));
@@ -230,8 +245,11 @@ void rope_bwd_slice(torch::Tensor dx, torch::Tensor cos_t, torch::Tensor sin_t,
   const int B = dx.size(0), T = dx.size(1), Hn = dx.size(2), D = dx.size(3);
   const long Ctot = dqkv.size(2);
   TORCH_CHECK(dqkv.size(0) == B && dqkv.size(1) == T
-              && col_off + (long)Hn * D <= Ctot && col_off % 2 == 0);
-  TORCH_CHECK(T <= 65535 && cos_t.size(0) >= T && cos_t.size(1) == D / 2);
+              && col_off + (long)Hn * D <= Ctot && col_off >= 0
+              && col_off % 2 == 0 && Ctot % 2 == 0);
+  TORCH_CHECK(D % 4 == 0 && T <= 65535 && rope_table_ok(cos_t, T, D)
+              && rope_table_ok(sin_t, T, D),
+              "rope: cos/sin must be contiguous device fp32 [>=T, D/2]");
   auto stream = at::cuda::getCurrentHIPStream();
   const int work = Hn * (D / 4);
   hipLaunchKernelGGL(rope_kernel, dim3((work + 255) / 256, T, B), dim3(256),
@@ -245,6 +263,8 @@ void rope_bwd_slice(torch::Tensor dx, torch::Tensor cos_t, torch::Tensor sin_t,
 torch::Tensor silu_mul_fwd(torch::Tensor g, torch::Tensor u) {
   TORCH_CHECK(g.is_cuda() && g.dtype() == torch::kBFloat16 && g.is_contiguous());
   TORCH_CHECK(g.numel() % 8 == 0, "silu_mul: numel must be divisible by 8");
+  TORCH_CHECK(bf16_like(u, g), "silu_mul: u must match g (device bf16, "
+              "contiguous, same numel)");
   auto out = torch::empty_like(g);
   long n8 = g.numel() / 8;
   auto stream = at::cuda::getCurrentHIPStream();
@@ -258,6 +278,12 @@ torch::Tensor silu_mul_fwd(torch::Tensor g, torch::Tensor u) {
 
 std::vector<torch::Tensor> silu_mul_bwd(torch::Tensor dout, torch::Tensor g,
                                         torch::Tensor u) {
+  TORCH_CHECK(g.is_cuda() && g.dtype() == torch::kBFloat16 && g.is_contiguous()
+              && g.numel() % 8 == 0,
+              "silu_mul_bwd: g must be contiguous device bf16, numel % 8 == 0");
+  TORCH_CHECK(bf16_like(u, g) && bf16_like(dout, g),
+              "silu_mul_bwd: u and dout must match g (device bf16, "
+              "contiguous, same numel)");
   auto dg = torch::empty_like(g);
   auto du = torch::empty_like(u);
   long n8 = g.numel() / 8;
@@ -293,8 +319,16 @@ torch::Tensor silu_mul_joint_fwd(torch::Tensor wv) {
 }
 
 torch::Tensor silu_mul_joint_bwd(torch::Tensor dout, torch::Tensor wv) {
-  TORCH_CHECK(dout.is_cuda() && dout.is_contiguous() && wv.is_contiguous());
+  TORCH_CHECK(wv.is_cuda() && wv.dtype() == torch::kBFloat16
+              && wv.is_contiguous() && wv.dim() >= 1,
+              "silu_mul_joint_bwd: wv must be contiguous device bf16");
   const long H = wv.size(-1) / 2;
+  TORCH_CHECK(wv.size(-1) % 2 == 0 && H % 8 == 0,
+              "silu_mul_joint: last dim must be 2*H with H %% 8 == 0");
+  TORCH_CHECK(dout.is_cuda() && dout.dtype() == torch::kBFloat16
+              && dout.is_contiguous() && dout.numel() * 2 == wv.numel(),
+              "silu_mul_joint_bwd: dout must be contiguous device bf16 with "
+              "half of wv's elements");
   auto dwv = torch::empty_like(wv);
   const long rows = wv.numel() / (2 * H);
   const long n8 = rows * (H / 8);

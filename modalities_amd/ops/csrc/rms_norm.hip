@@ -23,7 +23,9 @@ __global__ void rmsnorm_fwd_kernel(const unsigned short* __restrict__ x,
   unsigned short* yr = y + row * (long)H;
 
   float ss = 0.f;
-  const int vecH = H / 8;
+  // 16-byte vector loads need 16-byte aligned rows: only when H % 8 == 0
+  // (block-uniform branch); otherwise the scalar loops cover the whole row.
+  const int vecH = (H % 8 == 0) ? H / 8 : 0;
   const shortx8* xv = reinterpret_cast<const shortx8*>(xr);
   for (int i = threadIdx.x; i < vecH; i += BLOCK) {
     shortx8 v = xv[i];
@@ -174,7 +176,9 @@ __global__ void dw_reduce_kernel(const float* __restrict__ dw_part,
 std::vector<torch::Tensor> rmsnorm_fwd(torch::Tensor x, torch::Tensor w, double eps) {
   TORCH_CHECK(x.is_cuda() && x.dtype() == torch::kBFloat16, "x must be device bf16");
   TORCH_CHECK(x.dim() == 2 && x.is_contiguous());
-  TORCH_CHECK(w.dtype() == torch::kBFloat16 && w.is_contiguous());
+  TORCH_CHECK(w.is_cuda() && w.dtype() == torch::kBFloat16
+              && w.is_contiguous() && w.numel() == x.size(1),
+              "rmsnorm_fwd: w must be contiguous device bf16 [H]");
   const long N = x.size(0);
   const int H = x.size(1);
   auto y = torch::empty_like(x);
@@ -191,8 +195,21 @@ std::vector<torch::Tensor> rmsnorm_fwd(torch::Tensor x, torch::Tensor w, double 
 
 std::vector<torch::Tensor> rmsnorm_bwd(torch::Tensor dy, torch::Tensor x,
                                        torch::Tensor w, torch::Tensor invrms) {
+  TORCH_CHECK(x.is_cuda() && x.dtype() == torch::kBFloat16 && x.dim() == 2
+              && x.is_contiguous(),
+              "rmsnorm_bwd: x must be contiguous device bf16 [N,H]");
   const long N = x.size(0);
   const int H = x.size(1);
+  TORCH_CHECK(dy.is_cuda() && dy.dtype() == torch::kBFloat16
+              && dy.is_contiguous() && dy.dim() == 2 && dy.size(0) == N
+              && dy.size(1) == H,
+              "rmsnorm_bwd: dy must be contiguous device bf16 [N,H]");
+  TORCH_CHECK(w.is_cuda() && w.dtype() == torch::kBFloat16
+              && w.is_contiguous() && w.numel() == H,
+              "rmsnorm_bwd: w must be contiguous device bf16 [H]");
+  TORCH_CHECK(invrms.is_cuda() && invrms.dtype() == torch::kFloat32
+              && invrms.is_contiguous() && invrms.numel() == N,
+              "rmsnorm_bwd: invrms must be contiguous device fp32 [N]");
   auto dx = torch::empty_like(x);
   auto dw = torch::zeros({H}, x.options().dtype(torch::kFloat32));
   torch::Tensor dw_part;  // allocated after nblocks is known

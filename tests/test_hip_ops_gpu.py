@@ -107,7 +107,10 @@ def test_cross_entropy():
     ref.backward()
     scale = torch.tensor(1.0 / n_valid.item(), device=DEV)
     dlogits = EXT.cross_entropy_bwd(lb, targets, lse, scale, -100)
-    torch.testing.assert_close(dlogits.float(), lf.grad, rtol=5e-2, atol=1e-4)
+    # the softmax part of the gradient is ~1/(N*V) = 4e-8 per element: the
+    # absolute tolerance sits far below it, so a kernel that dropped that
+    # part (writing only the target column) fails
+    torch.testing.assert_close(dlogits.float(), lf.grad, rtol=5e-2, atol=1e-10)
 
 
 # ---------------- Flash attention -------------------------------------------
