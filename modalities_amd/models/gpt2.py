@@ -5,7 +5,7 @@ src/modalities/models/gpt2/gpt2_model.py:816-1020 — GQA with separate q/k/v
 projections, RoPE, optional QK-norm, pre-norm blocks, SwiGLU or GELU MLP,
 ABSOLUTE/NOPE/ROTARY positional modes, weight tying, divisibility checks),
 but the hot path is built on the modalities_amd HIP ops: K1 flash attention
-(GQA without KV repetition), K4 fused RoPE, K5 RMSNorm, K6 SwiGLU epilogue.
+(GQA without KV repetition), K4 fused RoPE, K5 RMSNorm / LayerNorm, K6 SwiGLU epilogue.
 Attention head_dim is sized for MFMA tiles (multiples of 16; 64/128 fast)."""
 
 import math
@@ -20,6 +20,7 @@ from modalities_amd.models.model import NNModel, SwiGLU
 from modalities_amd.ops import flash_attention, precompute_rope_cos_sin, rope_apply
 from modalities_amd.ops.attention import fused_qkv_rope_attention
 from modalities_amd.ops.backend import use_hip
+from modalities_amd.ops.layer_norm import LayerNorm
 from modalities_amd.ops.linear import TwoStreamLinear
 from modalities_amd.ops.rms_norm import RMSNorm
 
@@ -59,7 +60,7 @@ class LayerNormConfig(BaseModel):
 def make_norm(cfg: LayerNormConfig, ndim: int) -> nn.Module:
     if cfg.variant == LayerNormVariant.RMS_NORM:
         return RMSNorm(ndim, eps=cfg.eps)
-    return nn.LayerNorm(ndim, eps=cfg.eps, bias=cfg.bias)
+    return LayerNorm(ndim, eps=cfg.eps, bias=cfg.bias)
 
 
 class GPT2LLMConfig(BaseModel):

@@ -12,6 +12,7 @@ from pydantic import BaseModel, Field
 from modalities_amd.models.model import NNModel
 from modalities_amd.nn.attention import AttentionType, MultiHeadAttention
 from modalities_amd.nn.mlp import MLP
+from modalities_amd.ops.layer_norm import LayerNorm
 
 
 class VisionTransformerConfig(BaseModel):
@@ -53,11 +54,11 @@ class VisionTransformerBlock(nn.Module):
     def __init__(self, n_embd: int, n_head: int, ffn_hidden: int, bias: bool,
                  dropout: float):
         super().__init__()
-        self.norm1 = nn.LayerNorm(n_embd)
+        self.norm1 = LayerNorm(n_embd)
         self.attention = MultiHeadAttention(
             n_embd, n_head, bias=bias, dropout=dropout,
             attention_type=AttentionType.NON_CAUSAL_SELF_ATTENTION)
-        self.norm2 = nn.LayerNorm(n_embd)
+        self.norm2 = LayerNorm(n_embd)
         self.mlp = MLP(n_embd, ffn_hidden, dropout=dropout, bias=bias)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
@@ -87,7 +88,7 @@ class VisionTransformer(NNModel):
         self.blocks = nn.ModuleList([
             VisionTransformerBlock(n_embd, n_head, ffn_hidden, bias, dropout)
             for _ in range(n_layer)])
-        self.norm = nn.LayerNorm(n_embd)
+        self.norm = LayerNorm(n_embd)
         self.has_cls_token = add_cls_token
         self.head = nn.Linear(n_embd, n_classes, bias=bias) \
             if n_classes is not None else None

@@ -7,6 +7,7 @@ torch SDPA/LayerNorm/CE/AdamW) with hand-written gfx950 HIP kernels:
 - K1  flash_attention   : MFMA/LDS-tiled causal attention fwd+bwd, GQA-aware
 - K4  rope              : fused rotate-half RoPE on q,k
 - K5  rms_norm          : wave-level reduction norm fwd+bwd
+- K5  layer_norm        : register-resident row LayerNorm fwd+bwd (bf16)
 - K6  silu_mul          : SwiGLU gate epilogue
 - K8  cross_entropy     : fused log-softmax + NLL over the vocab
 - K9  fused_adamw       : multi-tensor AdamW update
@@ -24,6 +25,7 @@ from modalities_amd.ops.backend import (  # noqa: F401
     require_hip,
 )
 from modalities_amd.ops.rms_norm import rms_norm  # noqa: F401
+from modalities_amd.ops.layer_norm import LayerNorm, layer_norm  # noqa: F401
 from modalities_amd.ops.rope import precompute_rope_cos_sin, rope_apply  # noqa: F401
 from modalities_amd.ops.swiglu import silu_mul, silu_mul_joint  # noqa: F401
 from modalities_amd.ops.cross_entropy import fused_cross_entropy  # noqa: F401

@@ -19,6 +19,7 @@ OUT = OPS_DIR / "_hip_ops.so"
 
 SOURCES = [
     "rms_norm.hip",
+    "layer_norm.hip",
     "elementwise.hip",
     "cross_entropy.hip",
     "adamw.hip",

@@ -4,6 +4,13 @@
 std::vector<torch::Tensor> rmsnorm_fwd(torch::Tensor x, torch::Tensor w, double eps);
 std::vector<torch::Tensor> rmsnorm_bwd(torch::Tensor dy, torch::Tensor x,
                                        torch::Tensor w, torch::Tensor invrms);
+std::vector<torch::Tensor> layernorm_fwd(torch::Tensor x, torch::Tensor w,
+                                         c10::optional<torch::Tensor> b,
+                                         double eps);
+std::vector<torch::Tensor> layernorm_bwd(torch::Tensor dy, torch::Tensor x,
+                                         torch::Tensor w, torch::Tensor mean,
+                                         torch::Tensor rstd, bool has_bias);
+long layernorm_max_h();
 torch::Tensor rope_fwd(torch::Tensor x, torch::Tensor cos_t, torch::Tensor sin_t,
                        bool neg);
 torch::Tensor rope_fwd_slice(torch::Tensor qkv, torch::Tensor cos_t,
@@ -86,6 +93,15 @@ static int g_attn_impl = [] {
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rmsnorm_fwd", &rmsnorm_fwd, "RMSNorm forward (K5)");
   m.def("rmsnorm_bwd", &rmsnorm_bwd, "RMSNorm backward (K5)");
+  m.def("layernorm_fwd", &layernorm_fwd,
+        "LayerNorm forward (K5): (y, mean, rstd); b may be None",
+        py::arg("x"), py::arg("w"), py::arg("b"), py::arg("eps"));
+  m.def("layernorm_bwd", &layernorm_bwd,
+        "LayerNorm backward (K5): (dx, dw, db); db is empty without bias",
+        py::arg("dy"), py::arg("x"), py::arg("w"), py::arg("mean"),
+        py::arg("rstd"), py::arg("has_bias"));
+  m.def("layernorm_max_h", &layernorm_max_h,
+        "largest row length the LayerNorm kernels take");
   m.def("rope_fwd", &rope_fwd, "RoPE rotate-half (K4); neg=true => inverse");
   m.def("rope_fwd_slice", &rope_fwd_slice,
         "RoPE a head-block slice of fused QKV into a contiguous [B,T,H,D]");
