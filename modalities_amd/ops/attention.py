@@ -1,8 +1,12 @@
 """Flash-style causal attention (K1): MFMA/LDS-tiled fwd+bwd, GQA-aware.
 
-HIP kernels: csrc/attention_fwd.hip / csrc/attention_bwd.hip — online-softmax
-tiling per the CDNA4 guide (swapped QK^T for lane-local softmax rows,
-XOR-swizzled K LDS image, ds_read_b64_tr_b16 for V).
+HIP kernels: csrc/attention_v2.hip is the perf path (8 waves, 2 waves/SIMD;
+head_dim 64/80/128); csrc/attention_fwd.hip / csrc/attention_bwd.hip are the
+v1 generation kept for A/B (head_dim 64/128), selected with set_attn_impl /
+MA_ATTN_IMPL. Both use online-softmax tiling per the CDNA4 guide (swapped
+QK^T for lane-local softmax rows, ds_read_b64_tr_b16 for V; v1 XOR-swizzles
+the K LDS image, v2 pads the LDS pitch). The backward takes an optional dlse
+(gradient of the log-sum-exp output), folded into the delta preprocess.
 
 Replaces both attention paths of the reference (reference:
 src/modalities/models/gpt2/gpt2_model.py:595-658 — flash_attn_func wheel and
@@ -91,11 +95,18 @@ def _ensure_custom_op():
             ctx.save_for_backward(q, k, v, output[0], output[1])
             ctx.causal = causal
             ctx.q_offset = q_offset
+            # flash_attention drops lse: its grad arrives as None, not zeros
+            ctx.set_materialize_grads(False)
 
         def _bwd(ctx, grad_o, grad_lse):
             q, k, v, o, lse = ctx.saved_tensors
+            if grad_o is None:
+                grad_o = torch.zeros_like(o)
+            if grad_lse is not None:
+                grad_lse = grad_lse.contiguous()
             dq, dk, dv = hip_ext().attn_bwd(grad_o.contiguous(), q, k, v, o,
-                                            lse, ctx.causal, ctx.q_offset)
+                                            lse, ctx.causal, ctx.q_offset,
+                                            grad_lse)
             return dq, dk, dv, None, None
 
         _op.register_autograd(_bwd, setup_context=_setup)

@@ -76,6 +76,7 @@ __device__ __forceinline__ void c_layout_to_frags(const float* p, bf16x8* frag,
 __global__ void delta_kernel(const unsigned short* __restrict__ dout,
                              const unsigned short* __restrict__ o,
                              float* __restrict__ delta,
+                             const float* __restrict__ dlse,
                              long total_rows, int T, int H, int D) {
   const long row = (blockIdx.x * (long)blockDim.x + threadIdx.x) / WAVE_SIZE;
   const int lane = threadIdx.x & 63;
@@ -96,7 +97,9 @@ __global__ void delta_kernel(const unsigned short* __restrict__ dout,
     const long bt = row / H;
     const int t = (int)(bt % T);
     const long b = bt / T;
-    delta[((b * H) + h) * T + t] = acc;
+    const long idx = ((b * H) + h) * T + t;
+    // d(loss)/d(lse) enters dS as +P*dlse: fold it into delta
+    delta[idx] = dlse ? acc - dlse[idx] : acc;
   }
 }
 
@@ -682,10 +685,20 @@ __global__ __launch_bounds__(256) void dkdv_kernel(
 static std::vector<torch::Tensor> attn_bwd_impl(
     torch::Tensor dout, torch::Tensor q, torch::Tensor k, torch::Tensor v,
     torch::Tensor o, torch::Tensor lse, bool causal, long q_offset,
-    torch::Tensor dv, long dvp, long dvc) {
+    torch::Tensor dv, long dvp, long dvc,
+    c10::optional<torch::Tensor> dlse = c10::nullopt) {
   TORCH_CHECK(causal, "attn_bwd: only causal attention is implemented");
   TORCH_CHECK(q.is_cuda() && q.dtype() == torch::kBFloat16 && q.is_contiguous());
   const int B = q.size(0), T = q.size(1), Hq = q.size(2), D = q.size(3);
+  const float* dlse_p = nullptr;
+  if (dlse.has_value()) {
+    const torch::Tensor& g = *dlse;
+    TORCH_CHECK(g.is_cuda() && g.device() == q.device()
+                && g.dtype() == torch::kFloat32 && g.is_contiguous()
+                && g.dim() == 3 && g.size(0) == B && g.size(1) == Hq
+                && g.size(2) == T, "dlse must be contiguous fp32 [B,Hq,T]");
+    dlse_p = g.data_ptr<float>();
+  }
   const int Tkv = k.size(1), Hkv = k.size(2);
   const int q_off = (int)q_offset;
   const float scale = 1.0f / sqrtf((float)D);
@@ -701,7 +714,7 @@ static std::vector<torch::Tensor> attn_bwd_impl(
     hipLaunchKernelGGL(attnbwd::delta_kernel, dim3((unsigned)grid), dim3(block),
                        0, stream, (const unsigned short*)dout.data_ptr(),
                        (const unsigned short*)o.data_ptr(),
-                       delta.data_ptr<float>(), total_rows, T, Hq, D);
+                       delta.data_ptr<float>(), dlse_p, total_rows, T, Hq, D);
     HIP_CHECK_KERNEL();
   }
 
@@ -777,11 +790,12 @@ static std::vector<torch::Tensor> attn_bwd_impl(
 std::vector<torch::Tensor> attn_bwd(torch::Tensor dout, torch::Tensor q,
                                     torch::Tensor k, torch::Tensor v,
                                     torch::Tensor o, torch::Tensor lse,
-                                    bool causal, long q_offset) {
+                                    bool causal, long q_offset,
+                                    c10::optional<torch::Tensor> dlse) {
   auto dv = torch::empty_like(v);
   const long Hkv = v.size(2), D = v.size(3);
   auto r = attn_bwd_impl(dout, q, k, v, o, lse, causal, q_offset, dv,
-                         Hkv * D, 0);
+                         Hkv * D, 0, dlse);
   return {r[0], r[1], dv};
 }
 

@@ -1095,6 +1095,7 @@ void dkdv2_kernel(
 __global__ void delta2_kernel(const unsigned short* __restrict__ dout,
                               const unsigned short* __restrict__ o,
                               float* __restrict__ delta,
+                              const float* __restrict__ dlse,
                               long total_rows, int T, int H, int D) {
   const long row = (blockIdx.x * (long)blockDim.x + threadIdx.x) / WAVE_SIZE;
   const int lane = threadIdx.x & 63;
@@ -1115,7 +1116,9 @@ __global__ void delta2_kernel(const unsigned short* __restrict__ dout,
     const long bt = row / H;
     const int t = (int)(bt % T);
     const long b = bt / T;
-    delta[((b * H) + h) * T + t] = acc;
+    const long idx = ((b * H) + h) * T + t;
+    // d(loss)/d(lse) enters dS as +P*dlse: fold it into delta
+    delta[idx] = dlse ? acc - dlse[idx] : acc;
   }
 }
 
@@ -1188,7 +1191,8 @@ std::vector<torch::Tensor> attn_fwd2(torch::Tensor q, torch::Tensor k,
 static std::vector<torch::Tensor> attn_bwd2_impl(
     torch::Tensor dout, torch::Tensor q, torch::Tensor k, torch::Tensor v,
     torch::Tensor o, torch::Tensor lse, bool causal, long q_offset,
-    torch::Tensor dv, long dvp, long dvc) {
+    torch::Tensor dv, long dvp, long dvc,
+    c10::optional<torch::Tensor> dlse = c10::nullopt) {
   TORCH_CHECK(causal, "attn_bwd2: only causal attention is implemented");
   TORCH_CHECK(q.is_cuda() && q.dtype() == torch::kBFloat16 && q.dim() == 4
               && q.is_contiguous(), "q must be contiguous bf16 [B,T,Hq,D]");
@@ -1210,6 +1214,15 @@ static std::vector<torch::Tensor> attn_bwd2_impl(
               && lse.dtype() == torch::kFloat32 && lse.is_contiguous()
               && lse.dim() == 3 && lse.size(0) == B && lse.size(1) == Hq
               && lse.size(2) == T, "lse must be contiguous fp32 [B,Hq,T]");
+  const float* dlse_p = nullptr;
+  if (dlse.has_value()) {
+    const torch::Tensor& g = *dlse;
+    TORCH_CHECK(g.is_cuda() && g.device() == q.device()
+                && g.dtype() == torch::kFloat32 && g.is_contiguous()
+                && g.dim() == 3 && g.size(0) == B && g.size(1) == Hq
+                && g.size(2) == T, "dlse must be contiguous fp32 [B,Hq,T]");
+    dlse_p = g.data_ptr<float>();
+  }
   TORCH_CHECK(dv.is_cuda() && dv.device() == q.device()
               && dv.dtype() == torch::kBFloat16 && dv.is_contiguous()
               && dvc >= 0 && dvc + (long)Hkv * D <= dvp
@@ -1233,7 +1246,7 @@ static std::vector<torch::Tensor> attn_bwd2_impl(
     hipLaunchKernelGGL(attn2::delta2_kernel, dim3((unsigned)grid), dim3(block),
                        0, stream, (const unsigned short*)dout.data_ptr(),
                        (const unsigned short*)o.data_ptr(),
-                       delta.data_ptr<float>(), total_rows, T, Hq, D);
+                       delta.data_ptr<float>(), dlse_p, total_rows, T, Hq, D);
     HIP_CHECK_KERNEL();
   }
 
@@ -1352,12 +1365,13 @@ static std::vector<torch::Tensor> attn_bwd2_impl(
 std::vector<torch::Tensor> attn_bwd2(torch::Tensor dout, torch::Tensor q,
                                      torch::Tensor k, torch::Tensor v,
                                      torch::Tensor o, torch::Tensor lse,
-                                     bool causal, long q_offset) {
+                                     bool causal, long q_offset,
+                                     c10::optional<torch::Tensor> dlse) {
   // dv is always a fresh contiguous tensor (v itself may be a strided view)
   auto dv = torch::empty(v.sizes(), q.options());
   const long Hkv = v.size(2), D = v.size(3);
   auto r = attn_bwd2_impl(dout, q, k, v, o, lse, causal, q_offset, dv,
-                          Hkv * D, 0);
+                          Hkv * D, 0, dlse);
   return {r[0], r[1], dv};
 }
 

@@ -52,7 +52,8 @@ std::vector<torch::Tensor> attn_fwd(torch::Tensor q, torch::Tensor k,
 std::vector<torch::Tensor> attn_bwd(torch::Tensor dout, torch::Tensor q,
                                     torch::Tensor k, torch::Tensor v,
                                     torch::Tensor o, torch::Tensor lse,
-                                    bool causal, long q_offset);
+                                    bool causal, long q_offset,
+                                    c10::optional<torch::Tensor> dlse);
 torch::Tensor mfma_probe_32x32x16(torch::Tensor a, torch::Tensor b);
 torch::Tensor tr16_probe(long mode);
 std::vector<torch::Tensor> attn_fwd_ablate(torch::Tensor q, torch::Tensor k,
@@ -75,7 +76,8 @@ std::vector<torch::Tensor> attn_fwd2(torch::Tensor q, torch::Tensor k,
 std::vector<torch::Tensor> attn_bwd2(torch::Tensor dout, torch::Tensor q,
                                      torch::Tensor k, torch::Tensor v,
                                      torch::Tensor o, torch::Tensor lse,
-                                     bool causal, long q_offset);
+                                     bool causal, long q_offset,
+                                     c10::optional<torch::Tensor> dlse);
 std::vector<torch::Tensor> attn_bwd2_qkvjoint(torch::Tensor dout,
                                               torch::Tensor q, torch::Tensor k,
                                               torch::Tensor v, torch::Tensor o,
@@ -135,22 +137,30 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_bwd",
         [](torch::Tensor dout, torch::Tensor q, torch::Tensor k,
            torch::Tensor v, torch::Tensor o, torch::Tensor lse, bool causal,
-           long q_offset) {
+           long q_offset, c10::optional<torch::Tensor> dlse) {
           const long D = q.size(3);
           return (g_attn_impl == 2 || D == 80)
-              ? attn_bwd2(dout, q, k, v, o, lse, causal, q_offset)
-              : attn_bwd(dout, q, k, v, o, lse, causal, q_offset);
+              ? attn_bwd2(dout, q, k, v, o, lse, causal, q_offset, dlse)
+              : attn_bwd(dout, q, k, v, o, lse, causal, q_offset, dlse);
         },
-        "flash attention backward (K1)", py::arg("dout"), py::arg("q"),
+        "flash attention backward (K1); dlse = d(loss)/d(lse) fp32 [B,Hq,T] "
+        "or None", py::arg("dout"), py::arg("q"),
         py::arg("k"), py::arg("v"), py::arg("o"), py::arg("lse"),
-        py::arg("causal"), py::arg("q_offset") = 0);
+        py::arg("causal"), py::arg("q_offset") = 0,
+        py::arg("dlse") = py::none());
   m.def("set_attn_impl", [](long v) { g_attn_impl = (int)v; },
         "select the K1 kernel generation (1 or 2) for A/B");
   m.def("get_attn_impl", []() { return (long)g_attn_impl; });
   m.def("attn_fwd_v1", &attn_fwd, "K1 v1 forward (direct, for A/B)");
-  m.def("attn_bwd_v1", &attn_bwd, "K1 v1 backward (direct, for A/B)");
+  m.def("attn_bwd_v1", &attn_bwd, "K1 v1 backward (direct, for A/B)",
+        py::arg("dout"), py::arg("q"), py::arg("k"), py::arg("v"),
+        py::arg("o"), py::arg("lse"), py::arg("causal"), py::arg("q_offset"),
+        py::arg("dlse") = py::none());
   m.def("attn_fwd_v2", &attn_fwd2, "K1 v2 forward (direct, for A/B)");
-  m.def("attn_bwd_v2", &attn_bwd2, "K1 v2 backward (direct, for A/B)");
+  m.def("attn_bwd_v2", &attn_bwd2, "K1 v2 backward (direct, for A/B)",
+        py::arg("dout"), py::arg("q"), py::arg("k"), py::arg("v"),
+        py::arg("o"), py::arg("lse"), py::arg("causal"), py::arg("q_offset"),
+        py::arg("dlse") = py::none());
   m.def("tr16_probe", &tr16_probe, "ds_read_b64_tr_b16 semantics probe");
   m.def("mfma_probe_32x32x16", &mfma_probe_32x32x16,
         "MFMA fragment-layout probe (verification)");

@@ -278,28 +278,42 @@ def _merge_partials(o_a, lse_a, o_b, lse_b):
     return o_a.float() * w_a + o_b.float() * w_b, lse_new
 
 
+class _FlashWithLse(torch.autograd.Function):
+    """K1 kernel pair returning (o, lse), differentiable in BOTH outputs:
+    the ring merge weights exp(lse_s - lse_new) make the loss depend on lse,
+    and d(lse)/d(score) = P, so dS gains P * dlse — the backward kernels
+    take it folded into delta (delta - dlse)."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, q_offset):
+        from modalities_amd.ops.backend import hip_ext
+        o, lse = hip_ext().attn_fwd(q, k, v, True, q_offset)
+        ctx.save_for_backward(q, k, v, o, lse)
+        ctx.q_offset = q_offset
+        # an unused output (lse of a lone partial) arrives as None, not zeros
+        ctx.set_materialize_grads(False)
+        return o, lse
+
+    @staticmethod
+    def backward(ctx, do, dlse):
+        from modalities_amd.ops.backend import hip_ext
+        q, k, v, o, lse = ctx.saved_tensors
+        if do is None:
+            do = torch.zeros_like(o)
+        if dlse is not None:
+            dlse = dlse.contiguous()
+        dq, dk, dv = hip_ext().attn_bwd(do.contiguous(), q, k, v, o, lse,
+                                        True, ctx.q_offset, dlse)
+        return dq, dk, dv, None
+
+
 def _flash_with_lse(q, k, v, q_offset):
     """flash attention that also returns lse (natural log), differentiably.
     On device this is the K1 kernel pair; on CPU a fp32 composed path."""
     from modalities_amd.ops.backend import use_hip
     if use_hip(q, k, v):
-        from modalities_amd.ops.backend import hip_ext
-
-        class _WithLse(torch.autograd.Function):
-            @staticmethod
-            def forward(ctx, q_, k_, v_):
-                o, lse = hip_ext().attn_fwd(q_, k_, v_, True, q_offset)
-                ctx.save_for_backward(q_, k_, v_, o, lse)
-                return o, lse
-
-            @staticmethod
-            def backward(ctx, do, dlse):
-                q_, k_, v_, o, lse = ctx.saved_tensors
-                dq, dk, dv = hip_ext().attn_bwd(do.contiguous(), q_, k_, v_,
-                                                o, lse, True, q_offset)
-                return dq, dk, dv
-
-        return _WithLse.apply(q.contiguous(), k.contiguous(), v.contiguous())
+        return _FlashWithLse.apply(q.contiguous(), k.contiguous(),
+                                   v.contiguous(), q_offset)
     # composed fp32 path (CPU tests): compute scores once, derive o and lse
     import math
     B, T, Hq, D = q.shape
@@ -316,6 +330,33 @@ def _flash_with_lse(q, k, v, q_offset):
     return o, lse
 
 
+def _ring_local_attention(q_local, kv_at_step, cp_rank: int, cp_size: int,
+                          flash_with_lse=None) -> torch.Tensor:
+    """One rank's ring math, free of any process group. kv_at_step(s) returns
+    the stacked [2, B, Tl, Hkv, D] K/V chunk this rank holds at step s (chunk
+    (cp_rank - s) mod cp_size); it is called for EVERY s in 0..cp_size-1, in
+    order, so a communicating provider issues its exchanges identically on
+    all ranks. Partials: skipped for chunks after the rank's own, causal
+    (q_offset 0) for its own, unmasked (q_offset Tl) for earlier ones;
+    merged with the online-softmax rule and cast back to the input dtype.
+    flash_with_lse defaults to the production kernel pair; the test oracles
+    substitute an emulation and mutants."""
+    flash_with_lse = flash_with_lse or _flash_with_lse
+    Tl = q_local.shape[1]
+    o = lse = None
+    for s in range(cp_size):
+        kv_cur = kv_at_step(s)
+        chunk = (cp_rank - s) % cp_size
+        if chunk <= cp_rank:
+            off = Tl if chunk < cp_rank else 0  # full vs diagonal-causal
+            o_s, lse_s = flash_with_lse(q_local, kv_cur[0], kv_cur[1], off)
+            if o is None:
+                o, lse = o_s, lse_s
+            else:
+                o, lse = _merge_partials(o, lse, o_s, lse_s)
+    return o.to(q_local.dtype)
+
+
 def cp_attention_ring(q_local, k_local, v_local, group, cp_rank: int,
                       cp_size: int) -> torch.Tensor:
     """Ring CP (SURVEY.md §7 stage 9): K/V chunks rotate around the ring;
@@ -326,23 +367,21 @@ def cp_attention_ring(q_local, k_local, v_local, group, cp_rank: int,
     offset-causal kernel with q_offset = Tkv (mask allows every key)."""
     if cp_size == 1:
         return flash_attention(q_local, k_local, v_local, causal=True)
-    Tl = q_local.shape[1]
-    o = lse = None
     # K and V travel as ONE stacked tensor: a single sequential exchange
     # chain keeps every rank's backward collectives in the same order (two
     # independent chains could interleave k/v sends differently per rank).
     kv_cur = torch.stack((k_local, v_local))
-    for s in range(cp_size):
-        chunk = (cp_rank - s) % cp_size
-        if chunk <= cp_rank:
-            off = Tl if chunk < cp_rank else 0  # full vs diagonal-causal
-            o_s, lse_s = _flash_with_lse(q_local, kv_cur[0], kv_cur[1], off)
-            if o is None:
-                o, lse = o_s, lse_s
-            else:
-                o, lse = _merge_partials(o, lse, o_s, lse_s)
-        if s + 1 < cp_size:  # rotate K/V to the next rank
+    held_step = 0
+
+    def kv_at_step(s):
+        # called with s = 0 .. cp_size-1 in order: one exchange per new step
+        nonlocal kv_cur, held_step
+        while held_step < s:  # rotate K/V to the next rank
             kv_cur = _RingExchange.apply(kv_cur, group)
+            held_step += 1
+        return kv_cur
+
+    o = _ring_local_attention(q_local, kv_at_step, cp_rank, cp_size)
     # Tie the output to the end of the exchange chain: ranks whose queries
     # never attend to a received chunk still must run that exchange's
     # backward (it relays the K/V grads around the ring) — without the tie
@@ -350,4 +389,4 @@ def cp_attention_ring(q_local, k_local, v_local, group, cp_rank: int,
     # the input dtype: merged partials are fp32 (ADVICE r1 #1 — on the bf16
     # GPU path every rank that merged >=2 partials would otherwise hand
     # fp32 activations to the following c_proj GEMM).
-    return _GraphTie.apply(o.to(q_local.dtype), kv_cur)
+    return _GraphTie.apply(o, kv_cur)

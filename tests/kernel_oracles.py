@@ -30,7 +30,9 @@ Error bounds are derived from the arithmetic, never tuned:
   2^-12 max|ref| + 2^-18 C``; emul = the torch fp32 computation with P and
   dS rounded to bf16 before the matmuls and bf16 outputs; C = the largest
   sum of |terms| of the fp32 accumulation (the fp32 reduction rule above;
-  it only matters where the bf16 terms vanish, e.g. dq at T = 1).
+  it only matters where the bf16 terms vanish, e.g. dq at T = 1).  With a
+  gradient dlse of the lse output, dS = P (dP - delta + dlse) and the
+  |terms| gain P |dlse|; the bound formula is the same.
 * fast intrinsics (__expf, __powf, exp2): where a derived bound breaks on
   the GPU, ``require(..., baseline=...)`` allows 2x the error of the same
   operation done by PyTorch in fp32 (measured against the same fp64
@@ -572,7 +574,8 @@ def _reduce_rep(x, Hkv):
     return x.reshape(B, Hkv, Hq // Hkv, T, D).sum(2).permute(0, 2, 1, 3)
 
 
-def attn_ref64(q, k, v, off, do=None):
+def attn_ref64(q, k, v, off, do=None, dlse=None):
+    """dlse: optional fp32 [B,Hq,Tq] gradient of lse (d lse / d score = P)."""
     B, Tq, Hq, D = q.shape
     Tkv, Hkv = k.shape[1], k.shape[2]
     sc = 1.0 / math.sqrt(D)
@@ -593,6 +596,10 @@ def attn_ref64(q, k, v, off, do=None):
         dS = P * (dP - delta)
         E = P * (dod.abs() @ vd.abs().transpose(-1, -2)
                  + (dod.abs() * (P @ vd.abs())).sum(-1, keepdim=True))
+        if dlse is not None:
+            dl = dlse.double()[..., None]
+            dS = P * (dP - delta + dl)
+            E = E + P * dl.abs()
         r["dq"] = ((dS @ kd) * sc).permute(0, 2, 1, 3)
         r["dk"] = _reduce_rep((dS.transpose(-1, -2) @ qd) * sc, Hkv)
         r["dv"] = _reduce_rep(P.transpose(-1, -2) @ dod, Hkv)
@@ -648,10 +655,11 @@ def torch_attn_fwd(q, k, v, off, mut=None, tile=64, thr=8.0):
     return o, lse
 
 
-def torch_attn_bwd(do, q, k, v, o, lse, off, mut=None):
+def torch_attn_bwd(do, q, k, v, o, lse, off, mut=None, dlse=None):
     """The fp32 emulation: P, dS rounded to bf16 before the matmuls, bf16
     outputs.  Serves as `emul` in the backward bound and as the correct
-    CPU implementation; mut = mask_plus1 / mask_minus1."""
+    CPU implementation; mut = mask_plus1 / mask_minus1 / drop_dlse (the
+    gradient of the lse output ignored)."""
     B, Tq, Hq, D = q.shape
     Tkv, Hkv = k.shape[1], k.shape[2]
     sc = 1.0 / math.sqrt(D)
@@ -665,6 +673,8 @@ def torch_attn_bwd(do, q, k, v, o, lse, off, mut=None):
     P = torch.exp(s - lse.float()[..., None])
     dP = dof @ vf.transpose(-1, -2)
     delta = (dof * of).sum(-1, keepdim=True)
+    if dlse is not None and mut != "drop_dlse":
+        delta = delta - dlse.float()[..., None]
     dS = bf(P * (dP - delta)).float()
     dq = ((dS @ kf) * sc).permute(0, 2, 1, 3)
     dk = _reduce_rep((dS.transpose(-1, -2) @ qf) * sc, Hkv)
@@ -700,19 +710,20 @@ def attn_ramp_inputs(Tq, Tkv, D, step, device, B=1, Hq=2, Hkv=1, seed=0):
 class AttnCase:
     """Inputs + fp64 reference + fp32/bf16 emulation, computed once."""
 
-    def __init__(self, inp, off, backward=True):
+    def __init__(self, inp, off, backward=True, dlse=None):
         self.q, self.k, self.v, self.do = inp["q"], inp["k"], inp["v"], inp["do"]
         self.off = off
+        self.dlse = dlse
         self.slope = inp.get("slope")
         self.ref = attn_ref64(self.q, self.k, self.v, off,
-                              self.do if backward else None)
+                              self.do if backward else None, dlse)
         self.emul_err = None
         if backward:
             ref = self.ref
             self.o_in = bf(ref["o"]).contiguous()
             self.lse_in = ref["lse"].float().contiguous()
             e = torch_attn_bwd(self.do, self.q, self.k, self.v, self.o_in,
-                               self.lse_in, off)
+                               self.lse_in, off, dlse=dlse)
             self.emul_err = {n: (t.double() - ref[n]).abs().max().item()
                              for n, t in zip(("dq", "dk", "dv"), e)}
 
@@ -736,11 +747,14 @@ def check_attn_bwd(attn_bwd, case, o=None, lse=None,
     delta = rowsum(dO*O) is common to both and the 2x-emulation bound
     compares like with like (at Tq = 1 that error is a single random draw,
     and two independent draws differ by more than 2x now and then).  It also
-    makes the backward check independent of the forward kernel."""
+    makes the backward check independent of the forward kernel.  A case
+    with dlse calls attn_bwd(do, q, k, v, o, lse, off, dlse)."""
     if o is None:
         o, lse = case.o_in, case.lse_in
+    extra = () if case.dlse is None else (case.dlse,)
     got = dict(zip(("dq", "dk", "dv"),
-                   attn_bwd(case.do, case.q, case.k, case.v, o, lse, case.off)))
+                   attn_bwd(case.do, case.q, case.k, case.v, o, lse, case.off,
+                            *extra)))
     r, res = case.ref, {}
     for n in which:
         err = (got[n].double() - r[n]).abs().max().item()
