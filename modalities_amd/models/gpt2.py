@@ -18,7 +18,9 @@ from pydantic import BaseModel, Field, model_validator
 
 from modalities_amd.models.model import NNModel, SwiGLU
 from modalities_amd.ops import flash_attention, precompute_rope_cos_sin, rope_apply
-from modalities_amd.ops.attention import fused_qkv_rope_attention
+from modalities_amd.exceptions import ConfigError
+from modalities_amd.ops.attention import (_doc_visible, document_starts,
+                                          fused_qkv_rope_attention)
 from modalities_amd.ops.backend import use_hip
 from modalities_amd.ops.layer_norm import LayerNorm
 from modalities_amd.ops.linear import TwoStreamLinear
@@ -90,6 +92,13 @@ class GPT2LLMConfig(BaseModel):
     # 2.7B shapes). MI355X-first option; off by default for weight-name
     # compatibility (TP sharding requires the unfused layout).
     fused_qkv: bool = False
+    # Packed sequences: restrict causal attention to the query's own
+    # document (documents end with eod_token_id, which belongs to the
+    # document it closes). Positions are NOT reset at document starts: RoPE
+    # scores depend on i - j only, ABSOLUTE keeps the window positions.
+    # Not available together with TP/SP, PP or CP.
+    attention_document_masking: bool = False
+    eod_token_id: Optional[int] = None
     attention_norm_config: LayerNormConfig = LayerNormConfig()
     ffn_norm_config: LayerNormConfig = LayerNormConfig()
     lm_head_norm_config: LayerNormConfig = LayerNormConfig()
@@ -101,7 +110,25 @@ class GPT2LLMConfig(BaseModel):
             raise ValueError("n_head_q must be divisible by n_head_kv")
         if self.n_embd % self.n_head_q != 0:
             raise ValueError("n_embd must be divisible by n_head_q")
+        if self.attention_document_masking:
+            if self.eod_token_id is None:
+                raise ValueError(
+                    "attention_document_masking requires eod_token_id")
+            if not 0 <= self.eod_token_id < self.vocab_size:
+                raise ValueError(
+                    f"eod_token_id ({self.eod_token_id}) must be in "
+                    f"[0, vocab_size={self.vocab_size})")
         return self
+
+
+def refuse_document_masking(model, what: str) -> None:
+    """Document masking needs the token ids of the whole window at every
+    attention: raise where a parallelism wrapper cannot provide them."""
+    cfg = getattr(model, "config", None)
+    if getattr(cfg, "attention_document_masking", False):
+        raise ConfigError(
+            f"attention_document_masking=True is not supported with {what}; "
+            "turn the flag off or run without it")
 
 
 class CausalSelfAttention(nn.Module):
@@ -148,7 +175,10 @@ class CausalSelfAttention(nn.Module):
             self.q_norm = self.k_norm = None
 
     def forward(self, x: torch.Tensor, rope_cos: Optional[torch.Tensor],
-                rope_sin: Optional[torch.Tensor]) -> torch.Tensor:
+                rope_sin: Optional[torch.Tensor],
+                doc_start: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """doc_start: int32 [B, T] document mask (see ops.attention), or
+        None for plain causal attention."""
         B, T, C = x.shape
         kv_dim = self.head_dim * self.n_head_kv
         if self.fused_qkv:
@@ -159,7 +189,8 @@ class CausalSelfAttention(nn.Module):
                 # fused split+RoPE+attention (joint dqkv assembly in bwd)
                 y = fused_qkv_rope_attention(qkv, rope_cos, rope_sin,
                                              self.n_head_q, self.n_head_kv,
-                                             self.head_dim)
+                                             self.head_dim,
+                                             doc_start=doc_start)
                 return self.resid_dropout(self.c_proj(y.reshape(B, T, C)))
             q, k, v = qkv.split([C, kv_dim, kv_dim], dim=-1)
             q = q.view(B, T, self.n_head_q, self.head_dim)
@@ -175,7 +206,7 @@ class CausalSelfAttention(nn.Module):
         if rope_cos is not None:
             q = rope_apply(q, rope_cos, rope_sin)
             k = rope_apply(k, rope_cos, rope_sin)
-        y = self._attend(q, k, v)
+        y = self._attend(q, k, v, doc_start)
         y = y.reshape(B, T, C)
         return self.resid_dropout(self.c_proj(y))
 
@@ -224,22 +255,29 @@ class CausalSelfAttention(nn.Module):
             y = y.transpose(1, 2)
         return self.c_proj(y.reshape(B, T, C))
 
-    def _attend(self, q, k, v):
+    def _attend(self, q, k, v, doc_start=None):
         if self.attention_impl == AttentionImplementation.HIP_FLASH:
-            return flash_attention(q, k, v, causal=True)
+            return flash_attention(q, k, v, causal=True, doc_start=doc_start)
         # debug paths operate in [B, H, T, D]
         rep = self.n_head_q // self.n_head_kv
         qt = q.transpose(1, 2)
         kt = k.transpose(1, 2).repeat_interleave(rep, dim=1)
         vt = v.transpose(1, 2).repeat_interleave(rep, dim=1)
         if self.attention_impl == AttentionImplementation.PYTORCH_FLASH:
-            y = torch.nn.functional.scaled_dot_product_attention(
-                qt, kt, vt, is_causal=True,
-                dropout_p=self.dropout if self.training else 0.0)
+            if doc_start is not None:
+                y = torch.nn.functional.scaled_dot_product_attention(
+                    qt, kt, vt, attn_mask=_doc_visible(doc_start),
+                    dropout_p=self.dropout if self.training else 0.0)
+            else:
+                y = torch.nn.functional.scaled_dot_product_attention(
+                    qt, kt, vt, is_causal=True,
+                    dropout_p=self.dropout if self.training else 0.0)
         else:  # MANUAL
             att = qt @ kt.transpose(-2, -1) / math.sqrt(self.head_dim)
             mask = torch.ones(qt.shape[2], kt.shape[2], dtype=torch.bool,
                               device=qt.device).tril()
+            if doc_start is not None:
+                mask = _doc_visible(doc_start)
             att = att.masked_fill(~mask, float("-inf")).softmax(-1)
             y = att @ vt
         return y.transpose(1, 2)
@@ -274,8 +312,12 @@ class GPT2Block(nn.Module):
         else:
             self.mlp = TransformerMLP(cfg.n_embd, cfg.ffn_hidden, cfg.bias, cfg.dropout)
 
-    def forward(self, x, rope_cos, rope_sin):
-        x = x + self.attn(self.attention_norm(x), rope_cos, rope_sin)
+    def forward(self, x, rope_cos, rope_sin, doc_start=None):
+        if doc_start is None:
+            x = x + self.attn(self.attention_norm(x), rope_cos, rope_sin)
+        else:
+            x = x + self.attn(self.attention_norm(x), rope_cos, rope_sin,
+                              doc_start=doc_start)
         x = x + self.mlp(self.ffn_norm(x))
         return x
 
@@ -339,8 +381,14 @@ class GPT2LLM(NNModel):
             x = x + self.wpe(pos)
         x = self.drop(x)
         rope_cos, rope_sin = self._rope(T, x.device)
-        for block in self.blocks:
-            x = block(x, rope_cos, rope_sin)
+        if self.config.attention_document_masking:
+            # once per forward; device-side only (hipGraph-capturable)
+            doc_start = document_starts(input_ids, self.config.eod_token_id)
+            for block in self.blocks:
+                x = block(x, rope_cos, rope_sin, doc_start=doc_start)
+        else:
+            for block in self.blocks:
+                x = block(x, rope_cos, rope_sin)
         x = self.lm_head_norm(x)
         logits = self.lm_head(x)
         return {self.prediction_key: logits}

@@ -4,7 +4,8 @@ Replaces the dependency-provided kernels the reference framework leans on
 (reference: SURVEY.md §2.4 K1-K11 — flash-attn wheel, cuBLAS epilogues,
 torch SDPA/LayerNorm/CE/AdamW) with hand-written gfx950 HIP kernels:
 
-- K1  flash_attention   : MFMA/LDS-tiled causal attention fwd+bwd, GQA-aware
+- K1  flash_attention   : MFMA/LDS-tiled causal attention fwd+bwd, GQA-aware,
+                          optional per-document mask for packed sequences
 - K4  rope              : fused rotate-half RoPE on q,k
 - K5  rms_norm          : wave-level reduction norm fwd+bwd
 - K5  layer_norm        : register-resident row LayerNorm fwd+bwd (bf16)
@@ -29,5 +30,5 @@ from modalities_amd.ops.layer_norm import LayerNorm, layer_norm  # noqa: F401
 from modalities_amd.ops.rope import precompute_rope_cos_sin, rope_apply  # noqa: F401
 from modalities_amd.ops.swiglu import silu_mul, silu_mul_joint  # noqa: F401
 from modalities_amd.ops.cross_entropy import fused_cross_entropy  # noqa: F401
-from modalities_amd.ops.attention import flash_attention  # noqa: F401
+from modalities_amd.ops.attention import document_starts, flash_attention  # noqa: F401
 from modalities_amd.ops.adamw import fused_adamw_step  # noqa: F401

@@ -16,19 +16,105 @@ gpt2_model.py:550-593).
 
 Layout: q [B, T, Hq, D]; k, v [B, T, Hkv, D]; Hq % Hkv == 0. Causal only
 (decoder LM pretraining); the CPU fallback handles the general case for
-tests."""
+tests.
+
+Document masking (packed sequences): with doc_start [B, T] int32 given,
+query i sees exactly the keys doc_start[b, i] <= j <= i. `document_starts`
+derives it from the token ids (the eod token belongs to the document it
+ends). The v2 kernels take the bound per softmax row and its key-side mirror
+doc_end[b, j] (last query of j's document) in the dK/dV kernel; they skip
+the tiles outside a document, so the work falls from T^2/2 to about T*L/2
+for documents of length L. Positions are not reset at document starts."""
 
 import math
+import weakref
+from typing import Optional
 
 import torch
 
 from modalities_amd.ops.backend import use_hip, hip_ext
 
 
-def _attention_ref(q, k, v, causal=True, q_offset=None):
+def document_starts(input_ids: torch.Tensor, eod_token_id: int) -> torch.Tensor:
+    """int32 [B, T]: start[b, i] = max({0} U {p + 1 : p < i and
+    input_ids[b, p] == eod}) -- the first position of the document that
+    token i belongs to (an eod token closes its own document). Device-side
+    ops only: no host sync, capturable in a hipGraph."""
+    if input_ids.dim() != 2:
+        raise ValueError("document_starts: input_ids must be [B, T]")
+    B, T = input_ids.shape
+    pos = torch.arange(T, dtype=torch.int32, device=input_ids.device)
+    after_eod = torch.zeros(B, T, dtype=torch.bool, device=input_ids.device)
+    after_eod[:, 1:] = input_ids[:, :-1] == eod_token_id
+    first = torch.where(after_eod, pos, torch.zeros_like(pos))
+    return torch.cummax(first, dim=1).values.contiguous()
+
+
+def document_ends(doc_start: torch.Tensor) -> torch.Tensor:
+    """int32 [B, T]: end[b, j] = the last i with start[b, i] == start[b, j]
+    (the key-side bound the dK/dV kernel needs). Device-side ops only."""
+    B, T = doc_start.shape
+    pos = torch.arange(T, dtype=torch.int32, device=doc_start.device)
+    last = torch.ones(B, T, dtype=torch.bool, device=doc_start.device)
+    last[:, :-1] = doc_start[:, 1:] != doc_start[:, :-1]
+    cand = torch.where(last, pos, torch.full_like(pos, T - 1))
+    return torch.cummin(cand.flip(1), dim=1).values.flip(1).contiguous()
+
+
+_DOC_END_CACHE = None  # (weakref(doc_start), its version, doc_end)
+
+
+def _document_ends_cached(doc_start: torch.Tensor) -> torch.Tensor:
+    """document_ends, derived once per doc_start tensor: every layer of a
+    model hands over the same tensor, and so does a checkpoint recompute."""
+    global _DOC_END_CACHE
+    c = _DOC_END_CACHE
+    if c is not None and c[0]() is doc_start and c[1] == doc_start._version:
+        return c[2]
+    doc_end = document_ends(doc_start)
+    _DOC_END_CACHE = (weakref.ref(doc_start), doc_start._version, doc_end)
+    return doc_end
+
+
+def _doc_visible(doc_start: torch.Tensor) -> torch.Tensor:
+    """bool [B, 1, T, T]: key j visible to query i iff start[b,i] <= j <= i."""
+    T = doc_start.shape[1]
+    j = torch.arange(T, device=doc_start.device)
+    return ((j[None, None, :] >= doc_start[:, :, None])
+            & (j[None, None, :] <= j[None, :, None]))[:, None]
+
+
+def _check_doc_args(q, k, causal, q_offset, doc_start):
+    if not causal:
+        raise ValueError("doc_start requires causal=True")
+    if q.shape[1] != k.shape[1]:
+        raise ValueError(f"doc_start requires Tq == Tkv, got {q.shape[1]} "
+                         f"and {k.shape[1]}")
+    if q_offset not in (None, 0):
+        raise ValueError(f"doc_start requires q_offset 0 or None, got {q_offset}")
+    if not isinstance(doc_start, torch.Tensor) or doc_start.dtype != torch.int32:
+        raise TypeError("doc_start must be an int32 tensor")
+    if doc_start.device != q.device:
+        raise ValueError(f"doc_start is on {doc_start.device}, q on {q.device}")
+    if tuple(doc_start.shape) != (q.shape[0], q.shape[1]):
+        raise ValueError(f"doc_start must be [B, T] = "
+                         f"{(q.shape[0], q.shape[1])}, got {tuple(doc_start.shape)}")
+    if not doc_start.is_contiguous():
+        raise ValueError("doc_start must be contiguous")
+
+
+def _require_v2_for_doc():
+    if hip_ext().get_attn_impl() != 2:
+        raise RuntimeError("document masking needs the v2 attention kernels; "
+                           "the v1 generation is selected (set_attn_impl / "
+                           "MA_ATTN_IMPL)")
+
+
+def _attention_ref(q, k, v, causal=True, q_offset=None, doc_start=None):
     # q: [B, T, Hq, D], k/v: [B, S, Hkv, D] -> [B, T, Hq, D]; fp32 compute.
     # q_offset: global position of q row 0 relative to k row 0 (context
     # parallelism); default aligns the q block to the END of the keys.
+    # doc_start: int32 [B, T] document mask (dense here).
     B, T, Hq, D = q.shape
     S, Hkv = k.shape[1], k.shape[2]
     rep = Hq // Hkv
@@ -40,6 +126,8 @@ def _attention_ref(q, k, v, causal=True, q_offset=None):
         diag = (S - T) if q_offset is None else q_offset
         mask = torch.ones(T, S, dtype=torch.bool, device=q.device).tril(diag)
         att = att.masked_fill(~mask, float("-inf"))
+    if doc_start is not None:
+        att = att.masked_fill(~_doc_visible(doc_start), float("-inf"))
     att = att.softmax(-1)
     out = att @ vf                                          # [B,Hq,T,D]
     return out.permute(0, 2, 1, 3).to(q.dtype)
@@ -110,23 +198,99 @@ def _ensure_custom_op():
             return dq, dk, dv, None, None
 
         _op.register_autograd(_bwd, setup_context=_setup)
+
+        # document-masked variant: a second op, so the schema above stays
+        # as it is (causal, offset 0 and Tq == Tkv are implied)
+        @torch.library.custom_op("modalities_amd::flash_attention_doc",
+                                 mutates_args=())
+        def _op_doc(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
+                    doc_start: torch.Tensor, doc_end: torch.Tensor
+                    ) -> tuple[torch.Tensor, torch.Tensor]:
+            o, lse = hip_ext().attn_fwd_doc(q, k, v, True, 0, doc_start)
+            return o, lse
+
+        @_op_doc.register_fake
+        def _(q, k, v, doc_start, doc_end):
+            B, T, Hq, _ = q.shape
+            return (torch.empty_like(q),
+                    q.new_empty((B, Hq, T), dtype=torch.float32))
+
+        def _setup_doc(ctx, inputs, output):
+            q, k, v, doc_start, doc_end = inputs
+            ctx.save_for_backward(q, k, v, output[0], output[1], doc_start,
+                                  doc_end)
+            ctx.set_materialize_grads(False)
+
+        def _bwd_doc(ctx, grad_o, grad_lse):
+            q, k, v, o, lse, doc_start, doc_end = ctx.saved_tensors
+            if grad_o is None:
+                grad_o = torch.zeros_like(o)
+            if grad_lse is not None:
+                grad_lse = grad_lse.contiguous()
+            dq, dk, dv = hip_ext().attn_bwd_doc(
+                grad_o.contiguous(), q, k, v, o, lse, True, 0, doc_start,
+                doc_end, grad_lse)
+            return dq, dk, dv, None, None
+
+        _op_doc.register_autograd(_bwd_doc, setup_context=_setup_doc)
         _CUSTOM_OP_READY = True
     except Exception:  # older torch without torch.library.custom_op
         _CUSTOM_OP_READY = False
     return _CUSTOM_OP_READY
 
 
-from typing import Optional
+class _FlashAttnDocHip(torch.autograd.Function):
+    """Document-masked attention without torch.library (older torch)."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, doc_start, doc_end):
+        o, lse = hip_ext().attn_fwd_doc(q, k, v, True, 0, doc_start)
+        ctx.save_for_backward(q, k, v, o, lse, doc_start, doc_end)
+        return o
+
+    @staticmethod
+    def backward(ctx, do):
+        q, k, v, o, lse, doc_start, doc_end = ctx.saved_tensors
+        dq, dk, dv = hip_ext().attn_bwd_doc(do.contiguous(), q, k, v, o, lse,
+                                            True, 0, doc_start, doc_end)
+        return dq, dk, dv, None, None
 
 
 def flash_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
                     causal: bool = True,
-                    q_offset: Optional[int] = None) -> torch.Tensor:
+                    q_offset: Optional[int] = None,
+                    doc_start: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Causal flash attention. q: [B,T,Hq,D]; k,v: [B,S,Hkv,D].
 
     q_offset (context parallelism): global key position of q row 0; None =
     classic alignment (q block ends at the last key, i.e. offset S-T).
-    The HIP kernels handle Tq != Tkv and offsets natively."""
+    The HIP kernels handle Tq != Tkv and offsets natively.
+
+    doc_start (packed sequences): contiguous int32 [B, T] on q's device,
+    non-decreasing with doc_start[b, i] <= i (see `document_starts`); query
+    i then sees exactly the keys doc_start[b, i] <= j <= i. Needs
+    causal=True, Tq == Tkv, an offset of 0 or None, and the v2 kernels."""
+    if doc_start is not None:
+        _check_doc_args(q, k, causal, q_offset, doc_start)
+        if use_hip(q, k, v):
+            _require_v2_for_doc()
+            doc_end = _document_ends_cached(doc_start)
+            if _ensure_custom_op():
+                o, _ = torch.ops.modalities_amd.flash_attention_doc(
+                    q.contiguous(), k.contiguous(), v.contiguous(),
+                    doc_start, doc_end)
+                return o
+            return _FlashAttnDocHip.apply(q.contiguous(), k.contiguous(),
+                                          v.contiguous(), doc_start, doc_end)
+        if q.is_cuda:
+            rep = q.shape[2] // k.shape[2]
+            y = torch.nn.functional.scaled_dot_product_attention(
+                q.transpose(1, 2),
+                k.transpose(1, 2).repeat_interleave(rep, dim=1),
+                v.transpose(1, 2).repeat_interleave(rep, dim=1),
+                attn_mask=_doc_visible(doc_start))
+            return y.transpose(1, 2)
+        return _attention_ref(q, k, v, True, doc_start=doc_start)
     if use_hip(q, k, v):
         off = q_offset
         if off is None:
@@ -167,7 +331,7 @@ class _FusedQKVRopeAttn(torch.autograd.Function):
     q/k slice copies."""
 
     @staticmethod
-    def forward(ctx, qkv, cos, sin, Hq, Hkv, D):
+    def forward(ctx, qkv, cos, sin, Hq, Hkv, D, doc_start=None, doc_end=None):
         ext = hip_ext()
         B, T, _ = qkv.shape
         C, KV = Hq * D, Hkv * D
@@ -177,31 +341,52 @@ class _FusedQKVRopeAttn(torch.autograd.Function):
         # V stays a row-strided view into the joint activation: the v2
         # kernels read it in place (no per-layer 2*B*T*KV copy)
         v = qkv[..., C + KV:].view(B, T, Hkv, D)
-        o, lse = ext.attn_fwd(q, k, v, True, 0)
-        ctx.save_for_backward(q, k, v, o, lse, cos, sin)
+        if doc_start is None:
+            o, lse = ext.attn_fwd(q, k, v, True, 0)
+            ctx.save_for_backward(q, k, v, o, lse, cos, sin)
+        else:
+            o, lse = ext.attn_fwd_doc(q, k, v, True, 0, doc_start)
+            ctx.save_for_backward(q, k, v, o, lse, cos, sin, doc_start,
+                                  doc_end)
         ctx.dims = (Hq, Hkv, D)
         return o
 
     @staticmethod
     def backward(ctx, do):
-        q, k, v, o, lse, cos, sin = ctx.saved_tensors
+        q, k, v, o, lse, cos, sin, *doc = ctx.saved_tensors
         Hq, Hkv, D = ctx.dims
         C, KV = Hq * D, Hkv * D
         B, T = q.shape[0], q.shape[1]
         ext = hip_ext()
         dqkv = torch.empty(B, T, C + 2 * KV, dtype=q.dtype, device=q.device)
-        dq, dk = ext.attn_bwd_qkvjoint(do.contiguous(), q, k, v, o, lse,
-                                       True, 0, dqkv, C + KV)
+        if doc:
+            dq, dk = ext.attn_bwd_qkvjoint_doc(do.contiguous(), q, k, v, o,
+                                               lse, True, 0, doc[0], doc[1],
+                                               dqkv, C + KV)
+        else:
+            dq, dk = ext.attn_bwd_qkvjoint(do.contiguous(), q, k, v, o, lse,
+                                           True, 0, dqkv, C + KV)
         ext.rope_bwd_slice(dq, cos, sin, dqkv, 0)
         ext.rope_bwd_slice(dk, cos, sin, dqkv, C)
-        return dqkv, None, None, None, None, None
+        return dqkv, None, None, None, None, None, None, None
 
 
 def fused_qkv_rope_attention(qkv: torch.Tensor, cos: torch.Tensor,
                              sin: torch.Tensor, n_head_q: int, n_head_kv: int,
-                             head_dim: int) -> torch.Tensor:
+                             head_dim: int,
+                             doc_start: Optional[torch.Tensor] = None
+                             ) -> torch.Tensor:
     """Causal flash attention taking the joint QKV projection output
     directly; returns [B, T, n_head_q, head_dim]. HIP/GPU only — callers
-    fall back to split + rope_apply + flash_attention elsewhere."""
+    fall back to split + rope_apply + flash_attention elsewhere.
+    doc_start: the document mask of `flash_attention`, same contract."""
+    if doc_start is None:
+        return _FusedQKVRopeAttn.apply(qkv, cos, sin, n_head_q, n_head_kv,
+                                       head_dim)
+    if qkv.dim() != 3:
+        raise ValueError("qkv must be [B, T, Cq + 2*Ckv]")
+    _check_doc_args(qkv, qkv, True, 0, doc_start)
+    _require_v2_for_doc()
     return _FusedQKVRopeAttn.apply(qkv, cos, sin, n_head_q, n_head_kv,
-                                   head_dim)
+                                   head_dim, doc_start,
+                                   _document_ends_cached(doc_start))

@@ -21,6 +21,14 @@
 //     supported natively: contraction runs D/16 = 5 k-steps; LDS images
 //     keep the 128-column layout (stride DS) with the d >= 80 panels
 //     zeroed once; output stores masked to d < 80.
+//   - document masking (DOC = true instantiations): packed sequences carry
+//     a per-row lower key bound doc_start[b, i] (fwd/dq: key j visible iff
+//     doc_start[b, i] <= j <= i) and its key-side mirror doc_end[b, j]
+//     (dkdv: query i visible iff j <= i <= doc_end[b, j]). Both arrays are
+//     non-decreasing, so a wave's first/last row give wave-uniform bounds
+//     for the tile skip and the interior fast path, and a workgroup's kv
+//     (q) loop starts late (ends early). DOC = false compiles to exactly
+//     the causal kernels.
 //
 // Reference parity: replaces flash-attn 2.8.3 / SDPA
 // (src/modalities/models/gpt2/gpt2_model.py:595-658).
@@ -61,7 +69,7 @@ template <int D> struct Geom {
 // (K row-major XOR-swizzled; V as [DS/16][64][16] panels for tr reads).
 // Swapped QK^T (S^T = K Q^T) keeps softmax lane-local (guide T12);
 // defer-max rescale skip (T13, THR=8); exp2-domain state.
-template <int D_>
+template <int D_, bool DOC = false>
 struct FwdV2 {
   using G = Geom<D_>;
   static constexpr int D = D_, DS = G::DS, DP = G::DP;
@@ -134,6 +142,7 @@ struct FwdV2 {
                              unsigned short* __restrict__ o,
                              float* __restrict__ lse, int B, int Tq, int Tkv,
                              int q_off, int Hq, int Hkv, float scale,
+                             const int* __restrict__ doc_start,
                              char* smem_raw) {
     const int lane = threadIdx.x & 63;
     const int wid = threadIdx.x >> 6;
@@ -189,16 +198,36 @@ struct FwdV2 {
       for (int r = 0; r < 16; ++r) acc_o[dblk][r] = 0.f;
 
     const int q_hi_wg = min(qblk0 + WG_Q - 1, Tq - 1) + q_off;
-    const int n_tiles = (min(q_hi_wg, Tkv - 1)) / TKV + 1;
     // this wave's own causal bound (skip fully-masked tiles' compute)
     const int q_hi_wave = min(qblk0 + wid * QBLK + QBLK - 1, Tq - 1) + q_off;
     const int q_lo_wave = qblk0 + wid * QBLK + q_off;
 
+    // document mask (q_off == 0, Tq == Tkv): lo = this lane's first visible
+    // key; lo_first/lo_last = the wave's smallest/largest lo (doc_start is
+    // non-decreasing); the workgroup's kv loop starts at the tile holding
+    // the first row's document start (clamped: the array is only trusted
+    // for the mask, never for an address).
+    int lo = 0, lo_first = 0, lo_last = 0, tile0 = 0;
+    unsigned nvis = 0;
+    if constexpr (DOC) {
+      const int* ds = doc_start + (long)b * Tq;
+      lo = (qg < Tq) ? ds[qg] : 0;
+      // visible keys of this row: 0 <= kg - lo < nvis (one unsigned
+      // compare; implies kg <= qg < Tq == Tkv; rows >= Tq see nothing)
+      nvis = (qg < Tq) ? (unsigned)(qg - lo + 1) : 0u;
+      lo_first = ds[min(q_lo_wave, Tq - 1)];
+      lo_last = ds[q_hi_wave];
+      tile0 = max(0, min(ds[qblk0], qblk0)) / TKV;
+    }
+    // tiles tile0 .. tile0 + n_tiles - 1 are visited
+    const int n_tiles = (min(q_hi_wg, Tkv - 1)) / TKV + 1 - tile0;
+
     Stage st;
-    stage_load(st, k, v, kv_base, v_base, vp, 0, Tkv, Hkv);
+    stage_load(st, k, v, kv_base, v_base, vp, tile0 * TKV, Tkv, Hkv);
     stage_write(st, reinterpret_cast<Smem*>(smem_raw));
     __syncthreads();
-    if (n_tiles > 1) stage_load(st, k, v, kv_base, v_base, vp, TKV, Tkv, Hkv);
+    if (n_tiles > 1)
+      stage_load(st, k, v, kv_base, v_base, vp, (tile0 + 1) * TKV, Tkv, Hkv);
 
     const int lam = ln31 & 15;
     const unsigned trb0 = lds_addr(
@@ -208,7 +237,7 @@ struct FwdV2 {
 
 
     for (int tile = 0; tile < n_tiles; ++tile) {
-      const int kv0t = tile * TKV;
+      const int kv0t = (tile + tile0) * TKV;
       const bool stage_active = (kv0t <= q_hi_wave);
       const unsigned boff = (unsigned)(tile & 1) * BUF_BYTES;
       Smem* const sm = reinterpret_cast<Smem*>(smem_raw + boff);
@@ -219,7 +248,7 @@ struct FwdV2 {
         stage_write(st, reinterpret_cast<Smem*>(
             smem_raw + (unsigned)(~tile & 1) * BUF_BYTES));
         if (tile + 2 < n_tiles)
-          stage_load(st, k, v, kv_base, v_base, vp, (tile + 2) * TKV,
+          stage_load(st, k, v, kv_base, v_base, vp, (tile + 2 + tile0) * TKV,
                      Tkv, Hkv);
       }
 
@@ -227,6 +256,10 @@ struct FwdV2 {
         constexpr int sub = decltype(sub_)::value;
         const int kv0 = kv0t + KVBLK * sub;
         if (kv0 > q_hi_wave) return;  // sub fully masked for this wave
+        if constexpr (DOC) {
+          // every key of the sub precedes every row's document
+          if (kv0 + KVBLK - 1 < lo_first) return;
+        }
         // ---- S^T = K Q^T ------------------------------------------------
         floatx16 s0, s1;
 #pragma unroll
@@ -250,7 +283,8 @@ struct FwdV2 {
         float p[32];
         float tmax = -INFINITY;
         bool raw_scores = false;
-        if (kv0 + KVBLK - 1 <= q_lo_wave && kv0 + KVBLK <= Tkv && qg < Tq) {
+        if (kv0 + KVBLK - 1 <= q_lo_wave && kv0 + KVBLK <= Tkv && qg < Tq
+            && (!DOC || kv0 >= lo_last)) {
           raw_scores = true;
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
@@ -264,8 +298,16 @@ struct FwdV2 {
           for (int r = 0; r < 16; ++r) {
             const int kg0 = kv0 + crow(r, hi);
             const int kg1 = kv0 + 32 + crow(r, hi);
-            float v0 = (kg0 <= qgl && kg0 < Tkv) ? s0[r] * scale2 : -INFINITY;
-            float v1 = (kg1 <= qgl && kg1 < Tkv) ? s1[r] * scale2 : -INFINITY;
+            bool ok0, ok1;
+            if constexpr (DOC) {
+              ok0 = (unsigned)(kg0 - lo) < nvis;
+              ok1 = (unsigned)(kg1 - lo) < nvis;
+            } else {
+              ok0 = (kg0 <= qgl && kg0 < Tkv);
+              ok1 = (kg1 <= qgl && kg1 < Tkv);
+            }
+            float v0 = ok0 ? s0[r] * scale2 : -INFINITY;
+            float v1 = ok1 ? s1[r] * scale2 : -INFINITY;
             p[r] = v0;
             p[16 + r] = v1;
             tmax = fmaxf(tmax, fmaxf(v0, v1));
@@ -274,6 +316,11 @@ struct FwdV2 {
         tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
 
         // ---- online softmax with defer-max (T13) ------------------------
+        // (DOC: a row can meet a fully masked sub before its first visible
+        // key. Then tmax = m_run = -inf, tmax - m_run is NaN, the test is
+        // false and the rescale branch runs with alpha = 0 on l_run =
+        // acc_o = 0 and leaves m_run = -inf; p = exp2(-inf - 0) = 0. The
+        // first visible sub has tmax - m_run = +inf: never deferred.)
         constexpr float RESCALE_THR = 8.0f;
         const bool defer = __all(tmax - m_run <= RESCALE_THR);
         if (!defer) {
@@ -372,7 +419,7 @@ struct FwdV2 {
 // (K row + V row as S^T/dP^T A-operands; Kt panels as the dQ^T A-operand).
 // The kv tile is processed in two 32-row halves so only one (s, dp)
 // accumulator pair is live at a time (register budget).
-template <int D_>
+template <int D_, bool DOC = false>
 struct DQV2 {
   using G = Geom<D_>;
   static constexpr int D = D_, DS = G::DS, DP = G::DP;
@@ -444,6 +491,7 @@ struct DQV2 {
                              const float* lse, const float* delta,
                              unsigned short* dq, int B, int Tq, int Tkv,
                              int q_off, int Hq, int Hkv, float scale,
+                             const int* __restrict__ doc_start,
                              char* smem_raw) {
     const int lane = threadIdx.x & 63;
     const int wid = threadIdx.x >> 6;
@@ -500,15 +548,31 @@ struct DQV2 {
       for (int r = 0; r < 16; ++r) acc_dq[dblk][r] = 0.f;
 
     const int q_hi_wg = min(qblk0 + WG_Q - 1, Tq - 1) + q_off;
-    const int n_tiles = min(q_hi_wg, Tkv - 1) / TKV + 1;
     const int q_hi_wave = min(qblk0 + wid * QBLK + QBLK - 1, Tq - 1) + q_off;
     const int q_lo_wave = qblk0 + wid * QBLK + q_off;
 
+    // document mask: per-lane / wave-uniform lower key bounds and the
+    // workgroup's first kv tile (see FwdV2)
+    int lo = 0, lo_first = 0, lo_last = 0, tile0 = 0;
+    unsigned nvis = 0;
+    if constexpr (DOC) {
+      const int* ds = doc_start + (long)b * Tq;
+      lo = (qg < Tq) ? ds[qg] : 0;
+      // visible keys of this row: 0 <= kg - lo < nvis (one unsigned
+      // compare; implies kg <= qg < Tq == Tkv; rows >= Tq see nothing)
+      nvis = (qg < Tq) ? (unsigned)(qg - lo + 1) : 0u;
+      lo_first = ds[min(q_lo_wave, Tq - 1)];
+      lo_last = ds[q_hi_wave];
+      tile0 = max(0, min(ds[qblk0], qblk0)) / TKV;
+    }
+    const int n_tiles = min(q_hi_wg, Tkv - 1) / TKV + 1 - tile0;
+
     Stage st;
-    stage_load(st, k, v, kv_base, v_base, vp, 0, Tkv, Hkv);
+    stage_load(st, k, v, kv_base, v_base, vp, tile0 * TKV, Tkv, Hkv);
     stage_write(st, reinterpret_cast<Smem*>(smem_raw));
     __syncthreads();
-    if (n_tiles > 1) stage_load(st, k, v, kv_base, v_base, vp, TKV, Tkv, Hkv);
+    if (n_tiles > 1)
+      stage_load(st, k, v, kv_base, v_base, vp, (tile0 + 1) * TKV, Tkv, Hkv);
 
     const int lam = ln31 & 15;
     const unsigned trb0 = lds_addr(reinterpret_cast<Smem*>(smem_raw)->kt)
@@ -517,7 +581,7 @@ struct DQV2 {
 
 
     for (int tile = 0; tile < n_tiles; ++tile) {
-      const int kv0t = tile * TKV;
+      const int kv0t = (tile + tile0) * TKV;
       const bool stage_active = (kv0t <= q_hi_wave);
       const unsigned boff = (unsigned)(tile & 1) * BUF_BYTES;
       Smem* const sm = reinterpret_cast<Smem*>(smem_raw + boff);
@@ -527,7 +591,7 @@ struct DQV2 {
         stage_write(st, reinterpret_cast<Smem*>(
             smem_raw + (unsigned)(~tile & 1) * BUF_BYTES));
         if (tile + 2 < n_tiles)
-          stage_load(st, k, v, kv_base, v_base, vp, (tile + 2) * TKV,
+          stage_load(st, k, v, kv_base, v_base, vp, (tile + 2 + tile0) * TKV,
                      Tkv, Hkv);
       }
 
@@ -535,6 +599,9 @@ struct DQV2 {
         constexpr int sub = decltype(sub_)::value;
         const int kv0 = kv0t + KVBLK * sub;
         if (kv0 > q_hi_wave) return;  // sub fully masked for this wave
+        if constexpr (DOC) {
+          if (kv0 + KVBLK - 1 < lo_first) return;  // before every document
+        }
         attnc::static_for<2>([&](auto half_) {
           constexpr int half = decltype(half_)::value;
           const int kv0h = kv0 + 32 * half;
@@ -560,7 +627,8 @@ struct DQV2 {
 
           // dS'^T = scale * P .* (dP - delta), P = exp2(scale2*S' - lse2);
           // written back into dp_h (register-frugal)
-          if (kv0h + 31 <= q_lo_wave && kv0h + 32 <= Tkv && qg < Tq) {
+          if (kv0h + 31 <= q_lo_wave && kv0h + 32 <= Tkv && qg < Tq
+              && (!DOC || kv0h >= lo_last)) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
               const float p = __builtin_amdgcn_exp2f(
@@ -571,7 +639,10 @@ struct DQV2 {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
               const int kg = kv0h + crow(r, hi);
-              const float p = (kg <= qgl && kg < Tkv && qg < Tq)
+              bool ok;
+              if constexpr (DOC) ok = (unsigned)(kg - lo) < nvis;
+              else ok = (kg <= qgl && kg < Tkv && qg < Tq);
+              const float p = ok
                   ? __builtin_amdgcn_exp2f(fmaf(s_h[r], scale2, -my_lse2))
                   : 0.f;
               dp_h[r] = scale * p * (dp_h[r] - my_delta);
@@ -648,7 +719,7 @@ struct DQV2 {
 //   dP[q][kv]  = mfma(A=dO_lds, B=V_regs)
 //   dV[kv][d] += mfma(A=frags(P),   B=dOt)   col = d = ln31, rows kv = crow
 //   dK[kv][d] += mfma(A=frags(dS'), B=Qt)
-template <int D_, int MODE>
+template <int D_, int MODE, bool DOC = false>
 struct DKDVV2 {
   using G = Geom<D_>;
   static constexpr int D = D_, DS = G::DS;
@@ -760,6 +831,7 @@ struct DKDVV2 {
                              unsigned short* dk, unsigned short* dv,
                              int B, int Tq, int Tkv, int q_off, int Hq,
                              int Hkv, float scale, long dvp, long dvc,
+                             const int* __restrict__ doc_end,
                              char* smem_raw) {
     unsigned short* lds = reinterpret_cast<unsigned short*>(smem_raw);
     float* lse_s = reinterpret_cast<float*>(smem_raw + O_STATS);
@@ -825,7 +897,25 @@ struct DKDVV2 {
     // flattened (GQA q-head) x (q stage of TQ rows) iteration space with
     // incremental cursors (div/mod-free; see v1)
     const int first_qtile = max(0, kvblk0 - q_off) / TQ;
-    const int n_qtiles = (Tq + TQ - 1) / TQ;
+    // document mask (q_off == 0, Tq == Tkv): doc_end = last query that
+    // sees a kv row; he_first/he_last = the wave's smallest/largest
+    // doc_end (it is non-decreasing). The q range of the workgroup, for
+    // every GQA head of the group, ends at the stage holding doc_end of
+    // its last valid kv row (clamped into [that row, Tq-1]: the array is
+    // only trusted for the mask, never for an address).
+    int he_first = 0, he_last = 0, q_end = Tq - 1;
+    unsigned nvis = 0;
+    if constexpr (DOC) {
+      const int* de = doc_end + (long)b * Tkv;
+      // visible queries of this kv row: 0 <= qg - kvg < nvis (one unsigned
+      // compare; implies qg < Tq; rows >= Tkv are seen by nothing)
+      nvis = (kvg < Tkv) ? (unsigned)(min(de[kvg], Tq - 1) - kvg + 1) : 0u;
+      he_first = de[min(wv_kv0, Tkv - 1)];
+      he_last = de[min(wv_kv0 + QBLK - 1, Tkv - 1)];
+      const int kv_last = min(kvblk0 + WG_KV - 1, Tkv - 1);
+      q_end = min(max(de[kv_last], kv_last), Tq - 1);
+    }
+    const int n_qtiles = DOC ? q_end / TQ + 1 : (Tq + TQ - 1) / TQ;
     const int tiles_per_head = n_qtiles - first_qtile;
     const int n_iter = rep * tiles_per_head;
     const int q0_first = first_qtile * TQ;
@@ -903,6 +993,9 @@ struct DKDVV2 {
         constexpr int sub = decltype(sub_)::value;
         const int q0 = q0t + sub * QBLK;
         if (q0 + QBLK - 1 + q_off < wv_kv0) return;  // sub fully masked
+        if constexpr (DOC) {
+          if (q0 > he_last) return;  // past every kv row's document
+        }
         const float* lse_sub = lse_b + sub * 32;
         const float* delta_sub = delta_b + sub * 32;
         // S[q][kv], dP[q][kv] (col = kv = ln31, rows q = crow)
@@ -927,7 +1020,8 @@ struct DKDVV2 {
         // softmax back into the accumulator vectors (register-frugal:
         // s_acc becomes P; dp_acc becomes dS' when dK is computed)
         if (q0 + q_off >= wv_kv0 + QBLK && q0 + QBLK <= Tq
-            && wv_kv0 + QBLK <= Tkv) {
+            && wv_kv0 + QBLK <= Tkv
+            && (!DOC || q0 + QBLK - 1 <= he_first)) {
           // interior: every q row of this sub covers every kv row here
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
@@ -944,7 +1038,9 @@ struct DKDVV2 {
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
             const int qg = q0 + crow(r, hi);  // local
-            const bool ok = (qg < Tq) && (qg + q_off >= kvg) && (kvg < Tkv);
+            bool ok;
+            if constexpr (DOC) ok = (unsigned)(qg - kvg) < nvis;
+            else ok = (qg < Tq) && (qg + q_off >= kvg) && (kvg < Tkv);
             const float lq = lse_sub[crow(r, hi)];
             const float pv = ok
                 ? __builtin_amdgcn_exp2f(fmaf(s_acc[r], scale2k, -lq)) : 0.f;
@@ -1056,38 +1152,41 @@ struct DKDVV2 {
 };
 
 // ---------------------------------------------------------------------------
-template <int D>
+// doc_start / doc_end are read only by the DOC = true instantiations (the
+// causal launches pass nullptr).
+template <int D, bool DOC = false>
 __global__ __launch_bounds__(NT, 2) void fwd2_kernel(
     const unsigned short* q, const unsigned short* k, const unsigned short* v,
     long vp, unsigned short* o, float* lse, int B, int Tq, int Tkv, int q_off,
-    int Hq, int Hkv, float scale) {
+    int Hq, int Hkv, float scale, const int* doc_start) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  FwdV2<D>::run(q, k, v, vp, o, lse, B, Tq, Tkv, q_off, Hq, Hkv, scale,
-                smem_raw);
+  FwdV2<D, DOC>::run(q, k, v, vp, o, lse, B, Tq, Tkv, q_off, Hq, Hkv, scale,
+                     doc_start, smem_raw);
 }
 
-template <int D>
+template <int D, bool DOC = false>
 __global__ __launch_bounds__(NT, 2) void dq2_kernel(
     const unsigned short* q, const unsigned short* k, const unsigned short* v,
     long vp, const unsigned short* dout, const float* lse, const float* delta,
     unsigned short* dq, int B, int Tq, int Tkv, int q_off, int Hq, int Hkv,
-    float scale) {
+    float scale, const int* doc_start) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  DQV2<D>::run(q, k, v, vp, dout, lse, delta, dq, B, Tq, Tkv, q_off, Hq, Hkv,
-               scale, smem_raw);
+  DQV2<D, DOC>::run(q, k, v, vp, dout, lse, delta, dq, B, Tq, Tkv, q_off, Hq,
+                    Hkv, scale, doc_start, smem_raw);
 }
 
-template <int D, int MODE>
+template <int D, int MODE, bool DOC = false>
 __global__ __launch_bounds__((DKDVV2<D, MODE>::NTV),
                              ((MODE == 1 && D == 80) ? 3 : 2))
 void dkdv2_kernel(
     const unsigned short* q, const unsigned short* k, const unsigned short* v,
     long vp, const unsigned short* dout, const float* lse, const float* delta,
     unsigned short* dk, unsigned short* dv, int B, int Tq, int Tkv, int q_off,
-    int Hq, int Hkv, float scale, long dvp, long dvc) {
+    int Hq, int Hkv, float scale, long dvp, long dvc, const int* doc_end) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  DKDVV2<D, MODE>::run(q, k, v, vp, dout, lse, delta, dk, dv, B, Tq, Tkv,
-                       q_off, Hq, Hkv, scale, dvp, dvc, smem_raw);
+  DKDVV2<D, MODE, DOC>::run(q, k, v, vp, dout, lse, delta, dk, dv, B, Tq, Tkv,
+                            q_off, Hq, Hkv, scale, dvp, dvc, doc_end,
+                            smem_raw);
 }
 
 // delta preprocess: delta[b,h,t] = rowsum(dO * O) (local copy — device
@@ -1146,10 +1245,29 @@ static bool attn2_kv_ok(const torch::Tensor& q, const torch::Tensor& k,
       && (B == 1 || v.stride(0) == Tkv * v.stride(1));
 }
 
+// Document-mask bound array (doc_start or doc_end): int32 [B,T], contiguous,
+// on q's device. The kernels clamp what they use for addresses, so the
+// contents are not inspected here (no host sync).
+static void attn2_check_doc(const char* name, const torch::Tensor& t,
+                            const torch::Tensor& q, const torch::Tensor& k,
+                            bool causal, long q_offset) {
+  TORCH_CHECK(causal, name, ": document masking requires causal=True");
+  TORCH_CHECK(q_offset == 0, name,
+              ": document masking requires q_offset == 0, got ", q_offset);
+  TORCH_CHECK(q.dim() == 4 && k.dim() == 4 && q.size(1) == k.size(1), name,
+              ": document masking requires Tq == Tkv");
+  TORCH_CHECK(t.is_cuda() && t.device() == q.device(), name,
+              " must be on q's device");
+  TORCH_CHECK(t.dtype() == torch::kInt32, name, " must be int32");
+  TORCH_CHECK(t.dim() == 2 && t.size(0) == q.size(0)
+              && t.size(1) == q.size(1) && t.is_contiguous(), name,
+              " must be contiguous [B,T] matching q");
+}
+
 // ---------------------------------------------------------------------------
-std::vector<torch::Tensor> attn_fwd2(torch::Tensor q, torch::Tensor k,
-                                     torch::Tensor v, bool causal,
-                                     long q_offset) {
+static std::vector<torch::Tensor> attn_fwd2_impl(
+    torch::Tensor q, torch::Tensor k, torch::Tensor v, bool causal,
+    long q_offset, const int* doc_start) {
   TORCH_CHECK(causal, "attn_fwd2: only causal attention is implemented");
   TORCH_CHECK(q.is_cuda() && q.dtype() == torch::kBFloat16 && q.dim() == 4
               && q.is_contiguous(), "q must be contiguous bf16 [B,T,Hq,D]");
@@ -1179,20 +1297,48 @@ std::vector<torch::Tensor> attn_fwd2(torch::Tensor q, torch::Tensor k,
                        (const unsigned short*)k.data_ptr(),
                        (const unsigned short*)v.data_ptr(), vp,
                        (unsigned short*)o.data_ptr(), lse.data_ptr<float>(),
-                       B, Tq, Tkv, (int)q_offset, Hq, Hkv, scale);
+                       B, Tq, Tkv, (int)q_offset, Hq, Hkv, scale, doc_start);
   };
-  if (D == 128) launch(attn2::fwd2_kernel<128>, attn2::FwdV2<128>::SMEM_BYTES);
-  else if (D == 80) launch(attn2::fwd2_kernel<80>, attn2::FwdV2<80>::SMEM_BYTES);
-  else launch(attn2::fwd2_kernel<64>, attn2::FwdV2<64>::SMEM_BYTES);
+  if (doc_start != nullptr) {
+    if (D == 128)
+      launch(attn2::fwd2_kernel<128, true>, attn2::FwdV2<128>::SMEM_BYTES);
+    else if (D == 80)
+      launch(attn2::fwd2_kernel<80, true>, attn2::FwdV2<80>::SMEM_BYTES);
+    else
+      launch(attn2::fwd2_kernel<64, true>, attn2::FwdV2<64>::SMEM_BYTES);
+  } else if (D == 128) {
+    launch(attn2::fwd2_kernel<128>, attn2::FwdV2<128>::SMEM_BYTES);
+  } else if (D == 80) {
+    launch(attn2::fwd2_kernel<80>, attn2::FwdV2<80>::SMEM_BYTES);
+  } else {
+    launch(attn2::fwd2_kernel<64>, attn2::FwdV2<64>::SMEM_BYTES);
+  }
   HIP_CHECK_KERNEL();
   return {o, lse};
+}
+
+std::vector<torch::Tensor> attn_fwd2(torch::Tensor q, torch::Tensor k,
+                                     torch::Tensor v, bool causal,
+                                     long q_offset) {
+  return attn_fwd2_impl(q, k, v, causal, q_offset, nullptr);
+}
+
+// Document-masked causal forward: query i sees keys doc_start[b,i] <= j <= i.
+std::vector<torch::Tensor> attn_fwd2_doc(torch::Tensor q, torch::Tensor k,
+                                         torch::Tensor v, bool causal,
+                                         long q_offset,
+                                         torch::Tensor doc_start) {
+  attn2_check_doc("doc_start", doc_start, q, k, causal, q_offset);
+  return attn_fwd2_impl(q, k, v, causal, q_offset,
+                        doc_start.data_ptr<int>());
 }
 
 static std::vector<torch::Tensor> attn_bwd2_impl(
     torch::Tensor dout, torch::Tensor q, torch::Tensor k, torch::Tensor v,
     torch::Tensor o, torch::Tensor lse, bool causal, long q_offset,
     torch::Tensor dv, long dvp, long dvc,
-    c10::optional<torch::Tensor> dlse = c10::nullopt) {
+    c10::optional<torch::Tensor> dlse = c10::nullopt,
+    const int* doc_start = nullptr, const int* doc_end = nullptr) {
   TORCH_CHECK(causal, "attn_bwd2: only causal attention is implemented");
   TORCH_CHECK(q.is_cuda() && q.dtype() == torch::kBFloat16 && q.dim() == 4
               && q.is_contiguous(), "q must be contiguous bf16 [B,T,Hq,D]");
@@ -1278,7 +1424,7 @@ static std::vector<torch::Tensor> attn_bwd2_impl(
                        (const unsigned short*)dout.data_ptr(),
                        lse.data_ptr<float>(), delta.data_ptr<float>(),
                        (unsigned short*)dq.data_ptr(), B, T, Tkv, q_off, Hq,
-                       Hkv, scale);
+                       Hkv, scale, doc_start);
     HIP_CHECK_KERNEL();
   };
   auto launch_kv = [&](auto kfn, int wg_kv, int nthreads, size_t smem,
@@ -1292,11 +1438,36 @@ static std::vector<torch::Tensor> attn_bwd2_impl(
                        lse.data_ptr<float>(), delta.data_ptr<float>(),
                        (unsigned short*)dk.data_ptr(),
                        (unsigned short*)dv.data_ptr(), B, T, Tkv, q_off, Hq,
-                       Hkv, scale, dvp, dvc);
+                       Hkv, scale, dvp, dvc, doc_end);
     HIP_CHECK_KERNEL();
   };
   bool used_side2 = false;
-  if (D == 128) {
+  if (doc_start != nullptr) {
+    // document-masked instantiations; same kernel split per head_dim
+    if (D == 128) {
+      using DV = attn2::DKDVV2<128, 1>;
+      using DK = attn2::DKDVV2<128, 2>;
+      launch_dq(attn2::dq2_kernel<128, true>, attn2::DQV2<128>::SMEM_BYTES);
+      hipStreamWaitEvent(side2, ev_fork, 0);
+      used_side2 = true;
+      launch_kv(attn2::dkdv2_kernel<128, 1, true>, DV::WG_KV, DV::NTV,
+                DV::SMEM_BYTES, side);
+      launch_kv(attn2::dkdv2_kernel<128, 2, true>, DK::WG_KV, DK::NTV,
+                DK::SMEM_BYTES, side2);
+    } else if (D == 80) {
+      // fused only: it stays spill-free with the mask (252 registers), so
+      // the MA_DKDV80_SPLIT A/B pair is not instantiated for documents
+      using F = attn2::DKDVV2<80, 0>;
+      launch_dq(attn2::dq2_kernel<80, true>, attn2::DQV2<80>::SMEM_BYTES);
+      launch_kv(attn2::dkdv2_kernel<80, 0, true>, F::WG_KV, F::NTV,
+                F::SMEM_BYTES, side);
+    } else {
+      using F = attn2::DKDVV2<64, 0>;
+      launch_dq(attn2::dq2_kernel<64, true>, attn2::DQV2<64>::SMEM_BYTES);
+      launch_kv(attn2::dkdv2_kernel<64, 0, true>, F::WG_KV, F::NTV,
+                F::SMEM_BYTES, side);
+    }
+  } else if (D == 128) {
     // fused dkdv needs ~290 registers at D=128: run the register-clean
     // dV-only / dK-only kernels concurrently instead
     using DV = attn2::DKDVV2<128, 1>;
@@ -1388,5 +1559,43 @@ std::vector<torch::Tensor> attn_bwd2_qkvjoint(torch::Tensor dout,
               && dv_col_off + Hkv * D <= Ctot);
   auto r = attn_bwd2_impl(dout, q, k, v, o, lse, causal, q_offset, dqkv,
                           Ctot, dv_col_off);
+  return {r[0], r[1]};
+}
+
+// Document-masked backward: doc_start bounds the keys of a query row (dq),
+// doc_end the queries of a key row (dk, dv); both int32 [B,T].
+std::vector<torch::Tensor> attn_bwd2_doc(torch::Tensor dout, torch::Tensor q,
+                                         torch::Tensor k, torch::Tensor v,
+                                         torch::Tensor o, torch::Tensor lse,
+                                         bool causal, long q_offset,
+                                         torch::Tensor doc_start,
+                                         torch::Tensor doc_end,
+                                         c10::optional<torch::Tensor> dlse) {
+  attn2_check_doc("doc_start", doc_start, q, k, causal, q_offset);
+  attn2_check_doc("doc_end", doc_end, q, k, causal, q_offset);
+  TORCH_CHECK(v.dim() == 4, "v must be [B,Tkv,Hkv,D]");
+  auto dv = torch::empty(v.sizes(), q.options());
+  const long Hkv = v.size(2), D = v.size(3);
+  auto r = attn_bwd2_impl(dout, q, k, v, o, lse, causal, q_offset, dv,
+                          Hkv * D, 0, dlse, doc_start.data_ptr<int>(),
+                          doc_end.data_ptr<int>());
+  return {r[0], r[1], dv};
+}
+
+std::vector<torch::Tensor> attn_bwd2_qkvjoint_doc(
+    torch::Tensor dout, torch::Tensor q, torch::Tensor k, torch::Tensor v,
+    torch::Tensor o, torch::Tensor lse, bool causal, long q_offset,
+    torch::Tensor doc_start, torch::Tensor doc_end, torch::Tensor dqkv,
+    long dv_col_off) {
+  attn2_check_doc("doc_start", doc_start, q, k, causal, q_offset);
+  attn2_check_doc("doc_end", doc_end, q, k, causal, q_offset);
+  TORCH_CHECK(dqkv.is_cuda() && dqkv.dtype() == torch::kBFloat16
+              && dqkv.dim() == 3 && dqkv.is_contiguous() && v.dim() == 4);
+  const long Ctot = dqkv.size(2), Hkv = v.size(2), D = v.size(3);
+  TORCH_CHECK(dqkv.size(0) == v.size(0) && dqkv.size(1) == v.size(1)
+              && dv_col_off + Hkv * D <= Ctot);
+  auto r = attn_bwd2_impl(dout, q, k, v, o, lse, causal, q_offset, dqkv,
+                          Ctot, dv_col_off, c10::nullopt,
+                          doc_start.data_ptr<int>(), doc_end.data_ptr<int>());
   return {r[0], r[1]};
 }

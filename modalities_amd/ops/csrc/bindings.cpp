@@ -84,6 +84,22 @@ std::vector<torch::Tensor> attn_bwd2_qkvjoint(torch::Tensor dout,
                                               torch::Tensor lse, bool causal,
                                               long q_offset, torch::Tensor dqkv,
                                               long dv_col_off);
+std::vector<torch::Tensor> attn_fwd2_doc(torch::Tensor q, torch::Tensor k,
+                                         torch::Tensor v, bool causal,
+                                         long q_offset,
+                                         torch::Tensor doc_start);
+std::vector<torch::Tensor> attn_bwd2_doc(torch::Tensor dout, torch::Tensor q,
+                                         torch::Tensor k, torch::Tensor v,
+                                         torch::Tensor o, torch::Tensor lse,
+                                         bool causal, long q_offset,
+                                         torch::Tensor doc_start,
+                                         torch::Tensor doc_end,
+                                         c10::optional<torch::Tensor> dlse);
+std::vector<torch::Tensor> attn_bwd2_qkvjoint_doc(
+    torch::Tensor dout, torch::Tensor q, torch::Tensor k, torch::Tensor v,
+    torch::Tensor o, torch::Tensor lse, bool causal, long q_offset,
+    torch::Tensor doc_start, torch::Tensor doc_end, torch::Tensor dqkv,
+    long dv_col_off);
 
 // v1/v2 dispatch: v2 (8-wave, 2 waves/SIMD) is the perf path; v1 kept for
 // A/B and as a fallback switch. Flip with set_attn_impl / MA_ATTN_IMPL.
@@ -180,4 +196,54 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "attention backward writing dv into a fused-QKV grad buffer");
   m.def("attn_bwd_dkdv_ablate", &attn_bwd_dkdv_ablate,
         "attention bwd dkdv cost-attribution ablation (timing only)");
+  // Document-masked causal attention (packed sequences): v2 kernels only.
+  m.def("attn_fwd_doc",
+        [](torch::Tensor q, torch::Tensor k, torch::Tensor v, bool causal,
+           long q_offset, torch::Tensor doc_start) {
+          TORCH_CHECK(g_attn_impl == 2, "document masking needs the v2 "
+                      "attention kernels (set_attn_impl(2) / MA_ATTN_IMPL=2)");
+          return attn_fwd2_doc(q, k, v, causal, q_offset, doc_start);
+        },
+        "document-masked flash attention forward (K1): query i sees keys "
+        "doc_start[b,i] <= j <= i; doc_start int32 [B,T]",
+        py::arg("q"), py::arg("k"), py::arg("v"), py::arg("causal"),
+        py::arg("q_offset"), py::arg("doc_start"));
+  m.def("attn_bwd_doc",
+        [](torch::Tensor dout, torch::Tensor q, torch::Tensor k,
+           torch::Tensor v, torch::Tensor o, torch::Tensor lse, bool causal,
+           long q_offset, torch::Tensor doc_start, torch::Tensor doc_end,
+           c10::optional<torch::Tensor> dlse) {
+          TORCH_CHECK(g_attn_impl == 2, "document masking needs the v2 "
+                      "attention kernels (set_attn_impl(2) / MA_ATTN_IMPL=2)");
+          return attn_bwd2_doc(dout, q, k, v, o, lse, causal, q_offset,
+                               doc_start, doc_end, dlse);
+        },
+        "document-masked flash attention backward (K1); doc_end[b,j] = last "
+        "query that sees key j", py::arg("dout"), py::arg("q"), py::arg("k"),
+        py::arg("v"), py::arg("o"), py::arg("lse"), py::arg("causal"),
+        py::arg("q_offset"), py::arg("doc_start"), py::arg("doc_end"),
+        py::arg("dlse") = py::none());
+  m.def("attn_bwd_qkvjoint_doc",
+        [](torch::Tensor dout, torch::Tensor q, torch::Tensor k,
+           torch::Tensor v, torch::Tensor o, torch::Tensor lse, bool causal,
+           long q_offset, torch::Tensor doc_start, torch::Tensor doc_end,
+           torch::Tensor dqkv, long dv_col_off) {
+          TORCH_CHECK(g_attn_impl == 2, "document masking needs the v2 "
+                      "attention kernels (set_attn_impl(2) / MA_ATTN_IMPL=2)");
+          return attn_bwd2_qkvjoint_doc(dout, q, k, v, o, lse, causal,
+                                        q_offset, doc_start, doc_end, dqkv,
+                                        dv_col_off);
+        },
+        "document-masked attention backward writing dv into a fused-QKV "
+        "grad buffer");
+  m.def("attn_fwd_doc_v2", &attn_fwd2_doc,
+        "K1 v2 document-masked forward (direct)");
+  m.def("attn_bwd_doc_v2", &attn_bwd2_doc,
+        "K1 v2 document-masked backward (direct)", py::arg("dout"),
+        py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o"),
+        py::arg("lse"), py::arg("causal"), py::arg("q_offset"),
+        py::arg("doc_start"), py::arg("doc_end"),
+        py::arg("dlse") = py::none());
+  m.def("attn_bwd_qkvjoint_doc_v2", &attn_bwd2_qkvjoint_doc,
+        "K1 v2 document-masked joint-QKV backward (direct)");
 }

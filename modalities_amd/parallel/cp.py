@@ -191,6 +191,8 @@ def get_gpt2_context_parallel_model(model, device_mesh=None, group=None,
         group, cp_rank, cp_size = dim.group, dim.rank, dim.size
     if cp_size in (None, 1):
         return model
+    from modalities_amd.models.gpt2 import refuse_document_masking
+    refuse_document_masking(model, "context parallelism")
     if variant not in ("allgather", "ulysses", "ring"):
         raise ValueError(f"Unknown CP variant {variant!r}")
     for block in model.blocks:

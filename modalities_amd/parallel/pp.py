@@ -67,6 +67,8 @@ class GPT2PipelineStage(nn.Module):
 
     def __init__(self, full_model, stage_idx: int, blocks_per_stage: list[int]):
         super().__init__()
+        from modalities_amd.models.gpt2 import refuse_document_masking
+        refuse_document_masking(full_model, "pipeline parallelism")
         self.stage_idx = stage_idx
         self.num_stages = len(blocks_per_stage)
         self.is_first = stage_idx == 0

@@ -81,7 +81,9 @@ class HeadSegment(nn.Module):
 
 def gpt2_pipeline_segments(model) -> list[tuple[str, nn.Module]]:
     """Ordered single-tensor-boundary segments of a GPT2LLM."""
-    from modalities_amd.models.gpt2 import QueryKeyValueTransformType
+    from modalities_amd.models.gpt2 import (QueryKeyValueTransformType,
+                                            refuse_document_masking)
+    refuse_document_masking(model, "pipeline parallelism")
     cfg = model.config
     theta = cfg.rope_base \
         if cfg.qkv_transform == QueryKeyValueTransformType.ROTARY else None

@@ -412,6 +412,8 @@ def get_gpt2_tensor_parallelized_model(model, device_mesh=None, group=None,
         group, tp_rank, tp_size = dim.group, dim.rank, dim.size
     if tp_size in (None, 1):
         return model
+    from modalities_amd.models.gpt2 import refuse_document_masking
+    refuse_document_masking(model, "tensor/sequence parallelism")
     cfg = model.config
     if cfg.n_head_q % tp_size or cfg.n_head_kv % tp_size:
         raise ValueError(f"n_head_q ({cfg.n_head_q}) and n_head_kv "

@@ -49,6 +49,8 @@ def _get_save_list():
         from modalities_amd.ops.attention import _ensure_custom_op
         if _ensure_custom_op():
             _SAVE_LIST.add(torch.ops.modalities_amd.flash_attention.default)
+            _SAVE_LIST.add(
+                torch.ops.modalities_amd.flash_attention_doc.default)
     return _SAVE_LIST
 
 
