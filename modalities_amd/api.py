@@ -178,7 +178,8 @@ def _build_text_inference_component(config_path: Path):
         eod_token=gen_cfg.get("eod_token", "<eod>"),
         device=torch.device(settings.device),
         sample_key=settings.referencing_keys.get("sample_key", "input_ids"),
-        prediction_key=settings.referencing_keys.get("prediction_key", "logits"))
+        prediction_key=settings.referencing_keys.get("prediction_key", "logits"),
+        use_decode_graph=gen_cfg.get("use_decode_graph", True))
     return comp
 
 

@@ -4,7 +4,13 @@ templating, temperature/argmax sampling, incremental decode printing.
 
 MI355X-first improvement over the reference: a KV-cache-free full-context
 re-forward per token is kept as the simple default (matching the reference's
-behavior) but generation batches the forward on device in bf16."""
+behavior) but generation batches the forward on device in bf16.
+
+With a KV cache on the GPU, the per-token decode step reads its position
+from device counters (KVCache.pos_dev), so after the prefill one step is
+captured into a hipGraph (`DecodeGraph`) and replayed per token: the eager
+launch chain of a step is paid once. `use_decode_graph=False` opts out; a
+capture that fails falls back to the eager step."""
 
 import sys
 from typing import Optional
@@ -14,12 +20,80 @@ import torch
 from modalities_amd.tokenization.tokenizer_wrapper import TokenizerWrapper
 
 
+class DecodeGraph:
+    """One single-token `model.forward_cached` step on `cache`, captured
+    into a hipGraph after the prefill and replayed per token.
+
+    Static buffers: `ids` [B, 1] (write the next token here) and `logits`
+    [B, 1, V] (valid after `step`). Single stream; one warm-up step runs on
+    a side stream first and is then undone (the cache row it wrote is the
+    one the first replay rewrites). The host mirror cache.pos is advanced
+    per replay; the device counters advance inside the graph."""
+
+    def __init__(self, model, cache, sample_key: str, prediction_key: str):
+        self.cache = cache
+        self.sample_key = sample_key
+        dev = cache.pos_dev.device
+        B = cache.pos_dev.shape[0]
+        self.ids = torch.zeros(B, 1, dtype=torch.long, device=dev)
+        pos = cache.pos
+        if pos + 1 > cache.max_len:
+            raise ValueError("KV cache is full: nothing left to decode")
+
+        def rewind():
+            cache.pos = pos
+            cache.pos_dev.fill_(pos)
+
+        try:
+            side = torch.cuda.Stream(device=dev)
+            side.wait_stream(torch.cuda.current_stream(dev))
+            with torch.cuda.stream(side):
+                model.forward_cached({sample_key: self.ids}, cache)
+            torch.cuda.current_stream(dev).wait_stream(side)
+            rewind()
+            self.graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self.graph):
+                self.logits = model.forward_cached(
+                    {sample_key: self.ids}, cache)[prediction_key]
+        finally:
+            rewind()
+
+    def step(self, next_ids: torch.Tensor) -> torch.Tensor:
+        """Decode one token per row; returns the static logits [B, 1, V]."""
+        if self.cache.pos + 1 > self.cache.max_len:
+            raise ValueError(f"KV cache overflow: {self.cache.pos}+1 > "
+                             f"{self.cache.max_len}")
+        self.ids.copy_(next_ids)
+        self.graph.replay()
+        self.cache.pos += 1
+        return self.logits
+
+
+def capture_decode_graph(model, cache, sample_key: str = "input_ids",
+                         prediction_key: str = "logits"
+                         ) -> Optional[DecodeGraph]:
+    """A DecodeGraph when the model decodes on the GPU through the decode
+    kernels and the capture succeeds; None (decode eagerly) otherwise."""
+    route = getattr(model, "_decode_route", None)
+    if route is None or not cache.pos_dev.is_cuda \
+            or not route(cache.pos_dev):
+        return None
+    try:
+        return DecodeGraph(model, cache, sample_key, prediction_key)
+    except Exception as e:
+        print(f"# hipGraph capture of the decode step unavailable "
+              f"({type(e).__name__}: {e}); decoding eagerly",
+              file=sys.stderr, flush=True)
+        return None
+
+
 class TextInferenceComponent:
     def __init__(self, model, tokenizer: TokenizerWrapper, prompt_template: str,
                  sequence_length: int, temperature: float = 1.0,
                  eod_token: str = "<eod>", device: Optional[torch.device] = None,
                  sample_key: str = "input_ids", prediction_key: str = "logits",
-                 top_k: Optional[int] = None, top_p: Optional[float] = None):
+                 top_k: Optional[int] = None, top_p: Optional[float] = None,
+                 use_decode_graph: bool = True):
         self.model = model
         self.tokenizer = tokenizer
         self.prompt_template = prompt_template
@@ -31,6 +105,7 @@ class TextInferenceComponent:
         self.prediction_key = prediction_key
         self.top_k = top_k
         self.top_p = top_p
+        self.use_decode_graph = use_decode_graph
 
     def _sample(self, logits: torch.Tensor) -> torch.Tensor:
         """Greedy (temperature==0) or temperature sampling with optional
@@ -81,6 +156,8 @@ class TextInferenceComponent:
         else:
             out = self.model({self.sample_key: input_ids})
 
+        graph = None
+        graph_tried = not (self.use_decode_graph and cache is not None)
         for i in range(max_new):
             logits = out[self.prediction_key][:, -1, :].float()
             next_id = self._sample(logits)
@@ -96,8 +173,16 @@ class TextInferenceComponent:
             if cache is not None:
                 if cache.pos >= self.sequence_length:
                     break
-                out = self.model.forward_cached(
-                    {self.sample_key: next_id}, cache)
+                if not graph_tried:   # after the prefill, before step 1
+                    graph_tried = True
+                    graph = capture_decode_graph(
+                        self.model, cache, self.sample_key,
+                        self.prediction_key)
+                if graph is not None:
+                    out = {self.prediction_key: graph.step(next_id)}
+                else:
+                    out = self.model.forward_cached(
+                        {self.sample_key: next_id}, cache)
             else:
                 input_ids = torch.cat([input_ids, next_id], dim=1)
                 out = self.model({self.sample_key: input_ids})

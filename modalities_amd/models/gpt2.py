@@ -19,7 +19,10 @@ from pydantic import BaseModel, Field, model_validator
 from modalities_amd.models.model import NNModel, SwiGLU
 from modalities_amd.ops import flash_attention, precompute_rope_cos_sin, rope_apply
 from modalities_amd.exceptions import ConfigError
-from modalities_amd.ops.attention import (_doc_visible, document_starts,
+from modalities_amd.ops.attention import (DECODE_HEAD_DIMS, _doc_visible,
+                                          decode_attention,
+                                          decode_attention_enabled,
+                                          decode_rope_append, document_starts,
                                           fused_qkv_rope_attention)
 from modalities_amd.ops.backend import use_hip
 from modalities_amd.ops.layer_norm import LayerNorm
@@ -211,14 +214,23 @@ class CausalSelfAttention(nn.Module):
         return self.resid_dropout(self.c_proj(y))
 
     def forward_cached(self, x, rope_cos, rope_sin, cache_k, cache_v,
-                       pos: int):
+                       pos: int, dec=None):
         """Incremental-decode step: project the T_new tokens at absolute
         positions [pos, pos+T_new), append K/V into the preallocated cache,
         attend q against the cache prefix with q_offset=pos (the same
         offset-causal contract the CP path uses). Inference-only
         (no grad); MI355X-first addition — the reference re-forwards the
-        full context per generated token."""
+        full context per generated token.
+
+        dec = (pos_dev, lens_dev), int32 [B] device tensors holding pos and
+        pos + 1: a single-token step then takes the decode kernels, which
+        read the position from the device (no host value in a launch
+        argument, no slicing, no copy of the cache prefix)."""
         B, T, C = x.shape
+        if (dec is not None and T == 1
+                and self.attention_impl == AttentionImplementation.HIP_FLASH):
+            return self._forward_decode(x, rope_cos, rope_sin, cache_k,
+                                        cache_v, *dec)
         kv_dim = self.head_dim * self.n_head_kv
         if self.fused_qkv:
             qkv = self.qkv_attn(x)
@@ -254,6 +266,27 @@ class CausalSelfAttention(nn.Module):
                 qt, kt, vt, attn_mask=mask)
             y = y.transpose(1, 2)
         return self.c_proj(y.reshape(B, T, C))
+
+    def _forward_decode(self, x, rope_cos, rope_sin, cache_k, cache_v,
+                        pos_dev, lens_dev):
+        B, _, C = x.shape
+        kv_dim = self.head_dim * self.n_head_kv
+        if self.fused_qkv:
+            # q, k, v stay row-strided views into the joint projection
+            qkv = self.qkv_attn(x)
+            q, k, v = qkv.split([C, kv_dim, kv_dim], dim=-1)
+        else:
+            q, k, v = self.q_attn(x), self.k_attn(x), self.v_attn(x)
+        q = q.view(B, 1, self.n_head_q, self.head_dim)
+        k = k.view(B, 1, self.n_head_kv, self.head_dim)
+        v = v.view(B, 1, self.n_head_kv, self.head_dim)
+        if self.q_norm is not None:
+            q = self.q_norm(q)
+            k = self.k_norm(k)
+        q = decode_rope_append(q, k, v, rope_cos, rope_sin, pos_dev,
+                               cache_k, cache_v)
+        y = decode_attention(q, cache_k, cache_v, lens_dev)
+        return self.c_proj(y.reshape(B, 1, C))
 
     def _attend(self, q, k, v, doc_start=None):
         if self.attention_impl == AttentionImplementation.HIP_FLASH:
@@ -321,9 +354,15 @@ class GPT2Block(nn.Module):
         x = x + self.mlp(self.ffn_norm(x))
         return x
 
-    def forward_cached(self, x, rope_cos, rope_sin, cache_k, cache_v, pos):
-        x = x + self.attn.forward_cached(self.attention_norm(x), rope_cos,
-                                         rope_sin, cache_k, cache_v, pos)
+    def forward_cached(self, x, rope_cos, rope_sin, cache_k, cache_v, pos,
+                       dec=None):
+        if dec is None:
+            x = x + self.attn.forward_cached(self.attention_norm(x), rope_cos,
+                                             rope_sin, cache_k, cache_v, pos)
+        else:
+            x = x + self.attn.forward_cached(self.attention_norm(x), rope_cos,
+                                             rope_sin, cache_k, cache_v, pos,
+                                             dec=dec)
         x = x + self.mlp(self.ffn_norm(x))
         return x
 
@@ -410,12 +449,18 @@ class GPT2LLM(NNModel):
     def forward_cached(self, inputs: dict[str, torch.Tensor],
                        cache: "KVCache") -> dict[str, torch.Tensor]:
         """Forward only the NEW tokens; attends against the cached prefix.
-        Advances cache.pos. Logits are returned for the new tokens only."""
+        Advances cache.pos. Logits are returned for the new tokens only.
+
+        A single-token step on the GPU with the HIP attention takes the
+        decode route (`_decode_step`) unless `set_decode_attention(False)` /
+        MA_DECODE_ATTN=0 restores the route below."""
         input_ids = inputs[self.sample_key]
         B, T = input_ids.shape
         pos = cache.pos
         if pos + T > cache.max_len:
             raise ValueError(f"KV cache overflow: {pos}+{T} > {cache.max_len}")
+        if T == 1 and self._decode_route(input_ids):
+            return self._decode_step(input_ids, cache)
         x = self.wte(input_ids)
         if self.wpe is not None:
             p = torch.arange(pos, pos + T, dtype=torch.long,
@@ -426,12 +471,47 @@ class GPT2LLM(NNModel):
             x = block.forward_cached(x, rope_cos, rope_sin,
                                      cache.k[i], cache.v[i], pos)
         cache.pos = pos + T
+        cache.pos_dev.fill_(cache.pos)
+        x = self.lm_head_norm(x)
+        return {self.prediction_key: self.lm_head(x)}
+
+    def _decode_route(self, input_ids) -> bool:
+        cfg = self.config
+        return (input_ids.is_cuda and decode_attention_enabled()
+                and cfg.attention_implementation
+                == AttentionImplementation.HIP_FLASH
+                and cfg.n_embd // cfg.n_head_q in DECODE_HEAD_DIMS
+                and use_hip(input_ids))
+
+    def _decode_step(self, input_ids, cache: "KVCache"):
+        """One token per batch row at position cache.pos_dev. Every launch
+        reads the position from the device, so the step can be captured
+        into a hipGraph once and replayed per token; the host mirror
+        cache.pos only serves the overflow check (a replay advances it
+        itself, see inference/text_generation.py)."""
+        x = self.wte(input_ids)
+        if self.wpe is not None:
+            x = x + self.wpe(cache.pos_dev).unsqueeze(1)
+        torch.add(cache.pos_dev, 1, out=cache.lens_dev)
+        rope_cos, rope_sin = self._rope(cache.max_len, x.device)
+        dec = (cache.pos_dev, cache.lens_dev)
+        for i, block in enumerate(self.blocks):
+            x = block.forward_cached(x, rope_cos, rope_sin,
+                                     cache.k[i], cache.v[i], cache.pos,
+                                     dec=dec)
+        cache.pos_dev.add_(1)
+        cache.pos += 1
         x = self.lm_head_norm(x)
         return {self.prediction_key: self.lm_head(x)}
 
 
 class KVCache:
-    """Preallocated per-layer K/V buffers for incremental decoding."""
+    """Preallocated per-layer K/V buffers for incremental decoding.
+
+    `pos` is the host-side count of cached tokens; `pos_dev` (the same
+    value per batch row) and `lens_dev` (pos + 1 during a decode step: the
+    keys the new token attends to) are its int32 device mirrors, which the
+    decode kernels read so that a captured step can be replayed."""
 
     def __init__(self, n_layer: int, batch_size: int, max_len: int,
                  n_head_kv: int, head_dim: int, device, dtype):
@@ -443,6 +523,12 @@ class KVCache:
         self.v = [torch.zeros(batch_size, max_len, n_head_kv, head_dim,
                               device=device, dtype=dtype)
                   for _ in range(n_layer)]
+        self.pos_dev = torch.zeros(batch_size, dtype=torch.int32,
+                                   device=device)
+        self.lens_dev = torch.zeros(batch_size, dtype=torch.int32,
+                                    device=device)
 
     def reset(self):
         self.pos = 0
+        self.pos_dev.zero_()
+        self.lens_dev.zero_()

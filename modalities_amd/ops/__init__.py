@@ -5,7 +5,9 @@ Replaces the dependency-provided kernels the reference framework leans on
 torch SDPA/LayerNorm/CE/AdamW) with hand-written gfx950 HIP kernels:
 
 - K1  flash_attention   : MFMA/LDS-tiled causal attention fwd+bwd, GQA-aware,
-                          optional per-document mask for packed sequences
+                          optional per-document mask for packed sequences;
+                          split-KV single-token decode over a KV cache with
+                          a fused RoPE + cache append
 - K4  rope              : fused rotate-half RoPE on q,k
 - K5  rms_norm          : wave-level reduction norm fwd+bwd
 - K5  layer_norm        : register-resident row LayerNorm fwd+bwd (bf16)
@@ -31,4 +33,10 @@ from modalities_amd.ops.rope import precompute_rope_cos_sin, rope_apply  # noqa:
 from modalities_amd.ops.swiglu import silu_mul, silu_mul_joint  # noqa: F401
 from modalities_amd.ops.cross_entropy import fused_cross_entropy  # noqa: F401
 from modalities_amd.ops.attention import document_starts, flash_attention  # noqa: F401
+from modalities_amd.ops.attention import (  # noqa: F401
+    decode_attention,
+    decode_attention_enabled,
+    decode_rope_append,
+    set_decode_attention,
+)
 from modalities_amd.ops.adamw import fused_adamw_step  # noqa: F401

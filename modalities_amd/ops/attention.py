@@ -24,9 +24,19 @@ derives it from the token ids (the eod token belongs to the document it
 ends). The v2 kernels take the bound per softmax row and its key-side mirror
 doc_end[b, j] (last query of j's document) in the dK/dV kernel; they skip
 the tiles outside a document, so the work falls from T^2/2 to about T*L/2
-for documents of length L. Positions are not reset at document starts."""
+for documents of length L. Positions are not reset at document starts.
+
+Decoding (csrc/attention_decode.hip): `decode_attention` is single-token
+attention over a preallocated KV cache, split over the keys (one workgroup
+per batch row, kv head and chunk of keys, then a combine launch), with the
+per-row lengths in a device tensor; `decode_rope_append` rotates the new
+token's q and k at a device-side position and appends k and v to the cache
+in one launch. Neither takes a host-side position, so a decode step can be
+captured once into a hipGraph and replayed per token. `set_decode_attention`
+/ MA_DECODE_ATTN=0 switch the model back to the prefill kernel for A/B."""
 
 import math
+import os
 import weakref
 from typing import Optional
 
@@ -390,3 +400,147 @@ def fused_qkv_rope_attention(qkv: torch.Tensor, cos: torch.Tensor,
     return _FusedQKVRopeAttn.apply(qkv, cos, sin, n_head_q, n_head_kv,
                                    head_dim, doc_start,
                                    _document_ends_cached(doc_start))
+
+
+# ---------------------------------------------------------------------------
+# Decoding: split-KV single-token attention over a KV cache
+# ---------------------------------------------------------------------------
+
+_DECODE_ATTN = os.environ.get("MA_DECODE_ATTN", "1") != "0"
+
+DECODE_HEAD_DIMS = (64, 80, 128)
+
+
+def set_decode_attention(on: bool) -> None:
+    """Route single-token decode steps through the split-KV decode kernels
+    (default) or, with False, through the prefill kernel as before (A/B).
+    MA_DECODE_ATTN=0 sets the initial value."""
+    global _DECODE_ATTN
+    _DECODE_ATTN = bool(on)
+
+
+def decode_attention_enabled() -> bool:
+    return _DECODE_ATTN
+
+
+def _check_index_arg(name, t, ref, B):
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.int32:
+        raise TypeError(f"{name} must be an int32 tensor")
+    if t.device != ref.device:
+        raise ValueError(f"{name} is on {t.device}, q on {ref.device}")
+    if tuple(t.shape) != (B,):
+        raise ValueError(f"{name} must be [B] = {(B,)}, got {tuple(t.shape)}")
+    if not t.is_contiguous():
+        raise ValueError(f"{name} must be contiguous")
+
+
+def _check_decode_args(q, k_cache, v_cache, kv_lens):
+    if q.dim() != 4 or q.shape[1] != 1:
+        raise ValueError(f"q must be [B, 1, Hq, D], got {tuple(q.shape)}")
+    if k_cache.dim() != 4 or k_cache.shape != v_cache.shape:
+        raise ValueError("k_cache and v_cache must be [B, Lmax, Hkv, D] of "
+                         f"one shape, got {tuple(k_cache.shape)} and "
+                         f"{tuple(v_cache.shape)}")
+    B, _, Hq, D = q.shape
+    if k_cache.shape[0] != B or k_cache.shape[3] != D:
+        raise ValueError(f"caches {tuple(k_cache.shape)} do not match q "
+                         f"{tuple(q.shape)}")
+    if D not in DECODE_HEAD_DIMS:
+        raise ValueError(f"head_dim must be one of {DECODE_HEAD_DIMS}, got {D}")
+    Hkv = k_cache.shape[2]
+    if Hkv == 0 or Hq % Hkv != 0:
+        raise ValueError(f"Hq ({Hq}) must be a multiple of Hkv ({Hkv})")
+    if k_cache.device != q.device or v_cache.device != q.device:
+        raise ValueError("q and the caches must be on one device")
+    _check_index_arg("kv_lens", kv_lens, q, B)
+
+
+def _decode_attention_ref(q, k_cache, v_cache, kv_lens):
+    """Plain fp32 reference, one batch row at a time (reads the lengths on
+    the host)."""
+    Lmax = k_cache.shape[1]
+    o = torch.zeros_like(q)
+    for b, n in enumerate(kv_lens.tolist()):
+        n = min(max(n, 0), Lmax)
+        if n > 0:
+            o[b:b + 1] = _attention_ref(q[b:b + 1], k_cache[b:b + 1, :n],
+                                        v_cache[b:b + 1, :n], causal=True)
+    return o
+
+
+def decode_attention(q: torch.Tensor, k_cache: torch.Tensor,
+                     v_cache: torch.Tensor,
+                     kv_lens: torch.Tensor) -> torch.Tensor:
+    """Single-token attention over a KV cache. q: [B,1,Hq,D] (rows may be
+    strided); k_cache, v_cache: [B,Lmax,Hkv,D], read in place through their
+    strides; kv_lens: contiguous int32 [B] on q's device. Row b attends to
+    cache rows 0 .. kv_lens[b]-1 (clamped to [0, Lmax]; 0 gives zeros) and
+    nothing at or beyond the length is read. Returns o [B,1,Hq,D].
+    D in {64, 80, 128}; inference only (no autograd)."""
+    _check_decode_args(q, k_cache, v_cache, kv_lens)
+    if use_hip(q, k_cache, v_cache, kv_lens):
+        o, _ = hip_ext().decode_attn_fwd(q, k_cache, v_cache, kv_lens)
+        return o
+    return _decode_attention_ref(q, k_cache, v_cache, kv_lens)
+
+
+def _decode_rope_append_ref(q, k, v, cos, sin, pos, k_cache, v_cache):
+    Lmax = k_cache.shape[1]
+    ok = (pos >= 0) & (pos < Lmax)
+    idx = pos.clamp(0, Lmax - 1).long()
+    if cos is not None:
+        D = q.shape[-1]
+        c = torch.cat([cos[idx], cos[idx]], dim=-1).view(-1, 1, 1, D).float()
+        s = torch.cat([sin[idx], sin[idx]], dim=-1).view(-1, 1, 1, D).float()
+
+        def rot(x):
+            x1, x2 = x.float().chunk(2, dim=-1)
+            return (x.float() * c + torch.cat((-x2, x1), dim=-1) * s
+                    ).to(x.dtype)
+        q_out, k = rot(q), rot(k)
+    else:
+        q_out = q.clone()
+    q_out = torch.where(ok.view(-1, 1, 1, 1), q_out, torch.zeros_like(q_out))
+    rows = ok.nonzero().flatten()
+    k_cache[rows, idx[rows]] = k[rows, 0]
+    v_cache[rows, idx[rows]] = v[rows, 0]
+    return q_out.contiguous()
+
+
+def decode_rope_append(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
+                       cos: Optional[torch.Tensor],
+                       sin: Optional[torch.Tensor], pos: torch.Tensor,
+                       k_cache: torch.Tensor,
+                       v_cache: torch.Tensor) -> torch.Tensor:
+    """One decode step's RoPE and cache append. q: [B,1,Hq,D]; k, v:
+    [B,1,Hkv,D] (rows may be strided views, e.g. into the fused-QKV
+    projection output); cos/sin: fp32 [>=Lmax, D/2] tables or None (no
+    rotation); pos: contiguous int32 [B] on q's device. Rotates q and k at
+    table row pos[b], stores the rotated k and v to cache[b, pos[b]] and
+    returns the rotated q (contiguous). A row with pos[b] outside [0, Lmax)
+    leaves the cache untouched and returns zeros for q."""
+    if q.dim() != 4 or q.shape[1] != 1 or k.shape != v.shape \
+            or k.dim() != 4 or k.shape[:2] != q.shape[:2] \
+            or k.shape[3] != q.shape[3]:
+        raise ValueError("q must be [B,1,Hq,D] and k, v [B,1,Hkv,D], got "
+                         f"{tuple(q.shape)}, {tuple(k.shape)}, "
+                         f"{tuple(v.shape)}")
+    B, _, _, D = q.shape
+    if k_cache.dim() != 4 or k_cache.shape != v_cache.shape \
+            or (k_cache.shape[0], k_cache.shape[2], k_cache.shape[3]) \
+            != (B, k.shape[2], D):
+        raise ValueError(f"caches {tuple(k_cache.shape)} / "
+                         f"{tuple(v_cache.shape)} do not match k "
+                         f"{tuple(k.shape)}")
+    if (cos is None) != (sin is None):
+        raise ValueError("give both RoPE tables or neither")
+    if cos is not None and (cos.shape[0] < k_cache.shape[1]
+                            or cos.shape != sin.shape
+                            or cos.shape[1] != D // 2):
+        raise ValueError("cos/sin must be [>=Lmax, D/2], got "
+                         f"{tuple(cos.shape)} for Lmax={k_cache.shape[1]}")
+    _check_index_arg("pos", pos, q, B)
+    if use_hip(q, k, v, k_cache, v_cache, pos):
+        return hip_ext().decode_rope_append(q, k, v, cos, sin, pos, k_cache,
+                                            v_cache)
+    return _decode_rope_append_ref(q, k, v, cos, sin, pos, k_cache, v_cache)

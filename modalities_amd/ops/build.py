@@ -26,6 +26,7 @@ SOURCES = [
     "attention_fwd.hip",
     "attention_bwd.hip",
     "attention_v2.hip",
+    "attention_decode.hip",
     "bindings.cpp",
 ]
 

@@ -100,6 +100,19 @@ std::vector<torch::Tensor> attn_bwd2_qkvjoint_doc(
     torch::Tensor o, torch::Tensor lse, bool causal, long q_offset,
     torch::Tensor doc_start, torch::Tensor doc_end, torch::Tensor dqkv,
     long dv_col_off);
+std::vector<torch::Tensor> decode_attn_fwd(torch::Tensor q,
+                                           torch::Tensor k_cache,
+                                           torch::Tensor v_cache,
+                                           torch::Tensor kv_lens,
+                                           long kv_chunk);
+long decode_attn_kv_chunk();
+long decode_attn_kv_chunk_min();
+torch::Tensor decode_rope_append(torch::Tensor q, torch::Tensor k,
+                                 torch::Tensor v,
+                                 c10::optional<torch::Tensor> cos_t,
+                                 c10::optional<torch::Tensor> sin_t,
+                                 torch::Tensor pos, torch::Tensor k_cache,
+                                 torch::Tensor v_cache);
 
 // v1/v2 dispatch: v2 (8-wave, 2 waves/SIMD) is the perf path; v1 kept for
 // A/B and as a fallback switch. Flip with set_attn_impl / MA_ATTN_IMPL.
@@ -246,4 +259,23 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("dlse") = py::none());
   m.def("attn_bwd_qkvjoint_doc_v2", &attn_bwd2_qkvjoint_doc,
         "K1 v2 document-masked joint-QKV backward (direct)");
+  // Split-KV decode attention over a preallocated KV cache (inference).
+  m.def("decode_attn_fwd", &decode_attn_fwd,
+        "single-token attention: q [B,1,Hq,D] against cache rows "
+        "0..kv_lens[b]-1 (int32 [B] on the device), read in place; returns "
+        "(o, lse [B,Hq,1]). kv_chunk = 0 takes the default; an override "
+        "must be a multiple of 16 (smallest legal value 16)",
+        py::arg("q"), py::arg("k_cache"), py::arg("v_cache"),
+        py::arg("kv_lens"), py::arg("kv_chunk") = 0);
+  m.def("decode_attn_kv_chunk", &decode_attn_kv_chunk,
+        "default keys per workgroup of decode_attn_fwd");
+  m.def("decode_attn_kv_chunk_min", &decode_attn_kv_chunk_min,
+        "smallest legal kv_chunk override of decode_attn_fwd");
+  m.def("decode_rope_append", &decode_rope_append,
+        "RoPE the new token's q and k at table row pos[b] (None tables: no "
+        "rotation), store k and v to cache[b, pos[b]], return the rotated q; "
+        "rows with pos[b] outside [0, Lmax) leave the cache untouched",
+        py::arg("q"), py::arg("k"), py::arg("v"), py::arg("cos"),
+        py::arg("sin"), py::arg("pos"), py::arg("k_cache"),
+        py::arg("v_cache"));
 }

@@ -2,6 +2,13 @@
 re-forward on the flagship 2.7B shape (GPU).
 
     PYTHONPATH=. python tools/decode_bench.py [--ctx 512 2048 3968]
+        [--batch 1] [--impl {flash,split,graph}]
+
+--impl picks the route of the cached single-token step: `flash` is the
+prefill kernel on the copied cache prefix (set_decode_attention(False)),
+`split` the split-KV decode kernels launched eagerly (the default of
+forward_cached), `graph` the same step captured into a hipGraph and replayed
+(the default of text generation).
 """
 
 import argparse
@@ -25,24 +32,57 @@ def build_model():
     return m.to(torch.bfloat16).eval(), cfg
 
 
+def time_cached(model, ids, iters, impl):
+    """ms per generated token of the cached decode loop."""
+    from modalities_amd.inference.text_generation import DecodeGraph
+    from modalities_amd.ops import set_decode_attention
+    set_decode_attention(impl != "flash")
+    B, ctx = ids.shape
+    try:
+        cache = model.new_kv_cache(B, max_len=ctx + 2 * iters + 8)
+        out = model.forward_cached({"input_ids": ids}, cache)["logits"]
+        graph = None
+        if impl == "graph":
+            graph = DecodeGraph(model, cache, "input_ids", "logits")
+
+        def step(o):
+            nxt = o[:, -1:].argmax(-1)
+            if graph is not None:
+                return graph.step(nxt)
+            return model.forward_cached({"input_ids": nxt}, cache)["logits"]
+
+        for _ in range(4):          # warm every launch of the timed loop
+            out = step(out)
+        torch.cuda.synchronize()
+        t0 = time.time()
+        for _ in range(iters):
+            out = step(out)
+        torch.cuda.synchronize()
+        return (time.time() - t0) / iters * 1000
+    finally:
+        set_decode_attention(True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--ctx", type=int, nargs="+", default=[512, 2048, 3968])
     ap.add_argument("--iters", type=int, default=32)
+    ap.add_argument("--batch", type=int, default=1)
+    ap.add_argument("--impl", choices=["flash", "split", "graph"],
+                    default="split")
+    ap.add_argument("--no-reforward", action="store_true",
+                    help="skip the full-context re-forward comparison")
     args = ap.parse_args()
     model, cfg = build_model()
     for ctx in args.ctx:
-        ids = torch.randint(0, cfg.vocab_size, (1, ctx), device="cuda")
+        ids = torch.randint(0, cfg.vocab_size, (args.batch, ctx),
+                            device="cuda")
         with torch.no_grad():
-            cache = model.new_kv_cache(1, max_len=ctx + args.iters + 8)
-            out = model.forward_cached({"input_ids": ids}, cache)
-            torch.cuda.synchronize()
-            t0 = time.time()
-            for _ in range(args.iters):
-                nxt = out["logits"][:, -1:].argmax(-1)
-                out = model.forward_cached({"input_ids": nxt}, cache)
-            torch.cuda.synchronize()
-            cached_ms = (time.time() - t0) / args.iters * 1000
+            cached_ms = time_cached(model, ids, args.iters, args.impl)
+            if args.no_reforward:
+                print(f"ctx {ctx}: cached {cached_ms:.2f} ms/tok  "
+                      f"[batch {args.batch}, {args.impl}]")
+                continue
 
             full = ids
             out2 = model({"input_ids": full})
@@ -55,8 +95,11 @@ def main():
                 out2 = model({"input_ids": full})
             torch.cuda.synchronize()
             refwd_ms = (time.time() - t0) / n_ref * 1000
+        tag = "" if (args.batch, args.impl) == (1, "split") \
+            else f"  [batch {args.batch}, {args.impl}]"
         print(f"ctx {ctx}: cached {cached_ms:.1f} ms/tok  "
-              f"re-forward {refwd_ms:.1f} ms/tok  ({refwd_ms/cached_ms:.1f}x)")
+              f"re-forward {refwd_ms:.1f} ms/tok  ({refwd_ms/cached_ms:.1f}x)"
+              + tag)
 
 
 if __name__ == "__main__":
