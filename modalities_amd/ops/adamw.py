@@ -36,6 +36,22 @@ def fused_adamw_step(params: list, grads: list, exp_avgs: list, exp_avg_sqs: lis
 
 
 @torch.no_grad()
+def pack_wd_bits(mask: torch.Tensor):
+    """A 0/1 weight-decay mask (numel % 8 == 0) as a uint8 tensor with one
+    bit per element: bit j of byte i is element 8*i + j (numpy.packbits
+    with bitorder="little"), the form fused_adamw_devstep_bf16g reads.
+    None for a mask with any other value: it cannot be held in a bit.
+    Synchronizes (reads the check back): call outside the step."""
+    assert mask.numel() % 8 == 0, "mask length must be a multiple of 8"
+    if not bool(((mask == 0) | (mask == 1)).all()):
+        return None
+    weights = torch.tensor([1, 2, 4, 8, 16, 32, 64, 128], dtype=torch.int32,
+                           device=mask.device)
+    bits = ((mask != 0).reshape(-1, 8).to(torch.int32) * weights).sum(1)
+    return bits.to(torch.uint8)
+
+
+@torch.no_grad()
 def multi_tensor_l2norm(tensors: Iterable[torch.Tensor]) -> torch.Tensor:
     """Sum-of-squares -> local L2 norm over a list of tensors (one scalar)."""
     tensors = [t for t in tensors if t is not None]

@@ -3,6 +3,18 @@
 // L2-norm / scale. Replaces torch.optim.AdamW(fused=True)
 // (reference: optimizers/optimizer_factory.py:38-50) and
 // clip_grads_with_norm_ (fsdp_gradient_clipper.py:144-229).
+//
+// The device-step AdamW and the sum of squares each have ONE body,
+// instantiated for two input forms:
+//   <float grad, fp32 mask>    what any caller may hand in (fractional
+//                              masks, grads accumulated in fp32): 34 B/elem
+//   <bf16 grad, packed mask>   the engine's single-micro-batch fast path:
+//                              the reduced bf16 gradient is read where the
+//                              backward left it (no fp32 copy) and the
+//                              decay mask is one bit per element:
+//                              28.125 B/elem
+// bf16 -> fp32 is exact and the per-element expressions are shared, so the
+// two forms give bit-identical p, m, v and bf16 copy from equal values.
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 #include "common.h"
@@ -47,21 +59,57 @@ __device__ __forceinline__ float bias_correction(float beta, float t) {
   return -expm1f(t * logf(beta));
 }
 
+// Elements 4i..4i+3 of a gradient, as the fp32 values the update consumes.
+// fp32: as stored. bf16: 8 bytes per lane, widened (exact) and multiplied
+// by gmul, the 1/world factor the fp32 copy used to carry.
+__device__ __forceinline__ floatx4 load_grad4(const float* g, long i, float) {
+  return reinterpret_cast<const floatx4*>(g)[i];
+}
+
+__device__ __forceinline__ floatx4 load_grad4(const unsigned short* g, long i,
+                                              float gmul) {
+  const shortx4 h = reinterpret_cast<const shortx4*>(g)[i];
+  floatx4 r;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) r[j] = bf16_to_f32((unsigned short)h[j]) * gmul;
+  return r;
+}
+
+// Decay mask of elements 4i..4i+3. fp32: as stored (any value). Packed:
+// bit j of byte k is element 8k + j, so float4 i is the low or the high
+// nibble of byte i / 2; two neighbouring lanes read the same byte.
+__device__ __forceinline__ floatx4 load_mask4(const float* w, long i) {
+  return reinterpret_cast<const floatx4*>(w)[i];
+}
+
+__device__ __forceinline__ floatx4 load_mask4(const unsigned char* bits,
+                                              long i) {
+  const unsigned b = (unsigned)bits[i >> 1] >> ((unsigned)(i & 1) * 4u);
+  floatx4 r;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) r[j] = ((b >> j) & 1u) ? 1.0f : 0.0f;
+  return r;
+}
+
 // Graph-safe variant: the Adam step count lives in DEVICE memory so a
 // hipGraph replay of the training step sees the advancing bias correction
 // (a host-side bc baked into kernel args would be frozen at capture).
 // Also writes the bf16 working copy (bf16_out) in the same pass — fusing
 // the publish cast saves a full fp32 re-read + bf16 write of the params.
-__global__ void adamw_masked_devstep_kernel(float* __restrict__ p,
-                                            const float* __restrict__ g,
-                                            float* __restrict__ m,
-                                            float* __restrict__ v,
-                                            const float* __restrict__ wd_mask,
-                                            const int* __restrict__ step,
-                                            unsigned short* __restrict__ bf16_out,
-                                            const float* __restrict__ gscale,
-                                            long n4, float lr, float beta1,
-                                            float beta2, float eps, float wd) {
+// G: float or unsigned short (bf16 bits); W: float mask or packed bits.
+// The 1x float4 grid-stride shape measured best (320M elems: 5.6 TB/s,
+// against 5.1 and 3.9 for 2 and 4 float4 per thread).
+template <typename G, typename W>
+__global__ void adamw_devstep_kernel(float* __restrict__ p,
+                                     const G* __restrict__ g, float gmul,
+                                     float* __restrict__ m,
+                                     float* __restrict__ v,
+                                     const W* __restrict__ wd_mask,
+                                     const int* __restrict__ step,
+                                     unsigned short* __restrict__ bf16_out,
+                                     const float* __restrict__ gscale,
+                                     long n4, float lr, float beta1,
+                                     float beta2, float eps, float wd) {
   // gscale (device scalar, e.g. the grad-clip coefficient) is folded into
   // the grad read here — saves the separate full read+write scale pass
   // over every grad shard that multi_tensor_scale_ would cost.
@@ -72,13 +120,13 @@ __global__ void adamw_masked_devstep_kernel(float* __restrict__ p,
   const float step_size = lr / bc1;
   const float inv_bc2 = 1.0f / bc2;
   floatx4* p4 = reinterpret_cast<floatx4*>(p);
-  const floatx4* g4 = reinterpret_cast<const floatx4*>(g);
   floatx4* m4 = reinterpret_cast<floatx4*>(m);
   floatx4* v4 = reinterpret_cast<floatx4*>(v);
-  const floatx4* w4 = reinterpret_cast<const floatx4*>(wd_mask);
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n4;
        i += (long)gridDim.x * blockDim.x) {
-    floatx4 pp = p4[i], gg = g4[i], mm = m4[i], vv = v4[i], ww = w4[i];
+    floatx4 pp = p4[i], mm = m4[i], vv = v4[i];
+    const floatx4 gg = load_grad4(g, i, gmul);
+    const floatx4 ww = load_mask4(wd_mask, i);
     shortx4 h;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -94,68 +142,14 @@ __global__ void adamw_masked_devstep_kernel(float* __restrict__ p,
   }
 }
 
-template <int W>
-__global__ void adamw_devstep_wide_kernel(float* __restrict__ p,
-                                          const float* __restrict__ g,
-                                          float* __restrict__ m,
-                                          float* __restrict__ v,
-                                          const float* __restrict__ wd_mask,
-                                          const int* __restrict__ step,
-                                          unsigned short* __restrict__ bf16_out,
-                                          const float* __restrict__ gscale,
-                                          long n4, float lr, float beta1,
-                                          float beta2, float eps, float wd) {
-  const float gs = gscale ? *gscale : 1.0f;
-  const float t = (float)*step;
-  const float bc1 = bias_correction(beta1, t);
-  const float bc2 = bias_correction(beta2, t);
-  const float step_size = lr / bc1;
-  const float inv_bc2 = 1.0f / bc2;
-  floatx4* p4 = reinterpret_cast<floatx4*>(p);
-  const floatx4* g4 = reinterpret_cast<const floatx4*>(g);
-  floatx4* m4 = reinterpret_cast<floatx4*>(m);
-  floatx4* v4 = reinterpret_cast<floatx4*>(v);
-  const floatx4* w4 = reinterpret_cast<const floatx4*>(wd_mask);
-  const long stride = (long)gridDim.x * blockDim.x;
-  for (long i0 = ((long)blockIdx.x * blockDim.x + threadIdx.x) * W;
-       i0 < n4; i0 += stride * W) {
-    floatx4 pp[W], gg[W], mm[W], vv[W], ww[W];
-    shortx4 h[W];
-#pragma unroll
-    for (int u = 0; u < W; ++u)
-      if (i0 + u < n4) {
-        pp[u] = p4[i0 + u]; gg[u] = g4[i0 + u]; mm[u] = m4[i0 + u];
-        vv[u] = v4[i0 + u]; ww[u] = w4[i0 + u];
-      }
-#pragma unroll
-    for (int u = 0; u < W; ++u) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const float gj = gg[u][j] * gs;
-        pp[u][j] *= (1.0f - lr * wd * ww[u][j]);
-        mm[u][j] = beta1 * mm[u][j] + (1.0f - beta1) * gj;
-        vv[u][j] = beta2 * vv[u][j] + (1.0f - beta2) * gj * gj;
-        pp[u][j] -= step_size * mm[u][j] / (sqrtf(vv[u][j] * inv_bc2) + eps);
-        h[u][j] = (short)f32_to_bf16(pp[u][j]);
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < W; ++u)
-      if (i0 + u < n4) {
-        p4[i0 + u] = pp[u]; m4[i0 + u] = mm[u]; v4[i0 + u] = vv[u];
-        reinterpret_cast<shortx4*>(bf16_out)[i0 + u] = h[u];
-      }
-  }
-}
-
-__global__ void sqsum_kernel(const float* __restrict__ x, long n4,
+template <typename G>
+__global__ void sqsum_kernel(const G* __restrict__ x, float gmul, long n4,
                              float* __restrict__ out) {
   __shared__ float scratch[256 / WAVE_SIZE];
-  const floatx4* x4 = reinterpret_cast<const floatx4*>(x);
   float acc = 0.f;
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n4;
        i += (long)gridDim.x * blockDim.x) {
-    floatx4 v = x4[i];
+    floatx4 v = load_grad4(x, i, gmul);
 #pragma unroll
     for (int j = 0; j < 4; ++j) acc += v[j] * v[j];
   }
@@ -187,6 +181,13 @@ bool f32_like(const torch::Tensor& t, const torch::Tensor& ref) {
       && t.numel() == ref.numel() && t.device() == ref.device();
 }
 
+const float* gscale_ptr(const c10::optional<torch::Tensor>& gscale) {
+  if (!gscale.has_value()) return nullptr;
+  TORCH_CHECK(gscale->is_cuda() && gscale->dtype() == torch::kFloat32
+              && gscale->numel() == 1, "gscale must be a cuda fp32 scalar");
+  return gscale->data_ptr<float>();
+}
+
 }  // namespace
 
 void fused_adamw_masked(torch::Tensor p, torch::Tensor g, torch::Tensor m,
@@ -215,12 +216,7 @@ void fused_adamw_masked_devstep(torch::Tensor p, torch::Tensor g,
                                 c10::optional<torch::Tensor> gscale, double lr,
                                 double beta1, double beta2, double eps,
                                 double wd) {
-  const float* gs_ptr = nullptr;
-  if (gscale.has_value()) {
-    TORCH_CHECK(gscale->is_cuda() && gscale->dtype() == torch::kFloat32
-                && gscale->numel() == 1, "gscale must be a cuda fp32 scalar");
-    gs_ptr = gscale->data_ptr<float>();
-  }
+  const float* gs_ptr = gscale_ptr(gscale);
   TORCH_CHECK(p.is_cuda() && p.dtype() == torch::kFloat32 && p.is_contiguous());
   TORCH_CHECK(p.numel() % 4 == 0, "flat shard must be divisible by 4");
   TORCH_CHECK(f32_like(g, p) && f32_like(m, p) && f32_like(v, p)
@@ -232,41 +228,56 @@ void fused_adamw_masked_devstep(torch::Tensor p, torch::Tensor g,
               && bf16_out.is_contiguous() && bf16_out.numel() == p.numel());
   long n4 = p.numel() / 4;
   auto stream = at::cuda::getCurrentHIPStream();
-  static const int wide = []() {
-    const char* e = getenv("MODALITIES_AMD_ADAMW_WIDE");
-    // Isolated micro (320M elems): 1x float4 5.6 TB/s, 2x 5.1, 4x 3.9 —
-    // the narrow grid-stride form wins; wall-clock A/B showed no
-    // difference (the optimizer phase partially hides behind step tail).
-    return e ? atoi(e) : 1;
-  }();
-  if (wide >= 4) {
-    hipLaunchKernelGGL(adamw_devstep_wide_kernel<4>,
-                       dim3(grid_for((n4 + 3) / 4, 256)), dim3(256), 0, stream,
-                       p.data_ptr<float>(), g.data_ptr<float>(),
-                       m.data_ptr<float>(), v.data_ptr<float>(),
-                       wd_mask.data_ptr<float>(), step.data_ptr<int>(),
-                       (unsigned short*)bf16_out.data_ptr(), gs_ptr, n4,
-                       (float)lr, (float)beta1, (float)beta2, (float)eps,
-                       (float)wd);
-  } else if (wide >= 2) {
-    hipLaunchKernelGGL(adamw_devstep_wide_kernel<2>,
-                       dim3(grid_for((n4 + 1) / 2, 256)), dim3(256), 0, stream,
-                       p.data_ptr<float>(), g.data_ptr<float>(),
-                       m.data_ptr<float>(), v.data_ptr<float>(),
-                       wd_mask.data_ptr<float>(), step.data_ptr<int>(),
-                       (unsigned short*)bf16_out.data_ptr(), gs_ptr, n4,
-                       (float)lr, (float)beta1, (float)beta2, (float)eps,
-                       (float)wd);
-  } else {
-    hipLaunchKernelGGL(adamw_masked_devstep_kernel, dim3(grid_for(n4, 256)),
-                       dim3(256), 0, stream, p.data_ptr<float>(),
-                       g.data_ptr<float>(), m.data_ptr<float>(),
-                       v.data_ptr<float>(), wd_mask.data_ptr<float>(),
-                       step.data_ptr<int>(),
-                       (unsigned short*)bf16_out.data_ptr(), gs_ptr, n4,
-                       (float)lr, (float)beta1, (float)beta2, (float)eps,
-                       (float)wd);
-  }
+  hipLaunchKernelGGL((adamw_devstep_kernel<float, float>),
+                     dim3(grid_for(n4, 256)), dim3(256), 0, stream,
+                     p.data_ptr<float>(), g.data_ptr<float>(), 1.0f,
+                     m.data_ptr<float>(), v.data_ptr<float>(),
+                     wd_mask.data_ptr<float>(), step.data_ptr<int>(),
+                     (unsigned short*)bf16_out.data_ptr(), gs_ptr, n4,
+                     (float)lr, (float)beta1, (float)beta2, (float)eps,
+                     (float)wd);
+  HIP_CHECK_KERNEL();
+}
+
+// The fast path of the sharded engine: g is the reduced bf16 gradient as the
+// backward left it, used as float(g) * gmul (then * gscale); wd_bits holds
+// the 0/1 decay mask, bit j of byte i for element 8i + j.
+void fused_adamw_devstep_bf16g(torch::Tensor p, torch::Tensor g, double gmul,
+                               torch::Tensor m, torch::Tensor v,
+                               torch::Tensor wd_bits, torch::Tensor step,
+                               torch::Tensor bf16_out,
+                               c10::optional<torch::Tensor> gscale, double lr,
+                               double beta1, double beta2, double eps,
+                               double wd) {
+  const float* gs_ptr = gscale_ptr(gscale);
+  TORCH_CHECK(p.is_cuda() && p.dtype() == torch::kFloat32 && p.is_contiguous());
+  TORCH_CHECK(p.numel() % 8 == 0,
+              "flat shard must be divisible by 8 (one mask byte per 8)");
+  TORCH_CHECK(f32_like(m, p) && f32_like(v, p),
+              "m, v must match p (device fp32, contiguous)");
+  TORCH_CHECK(g.is_cuda() && g.dtype() == torch::kBFloat16 && g.is_contiguous()
+              && g.numel() == p.numel() && g.device() == p.device(),
+              "g must be a contiguous device bf16 tensor of p's size");
+  TORCH_CHECK(wd_bits.is_cuda() && wd_bits.dtype() == torch::kUInt8
+              && wd_bits.is_contiguous() && wd_bits.numel() * 8 == p.numel()
+              && wd_bits.device() == p.device(),
+              "wd_bits must be a contiguous device uint8 tensor of "
+              "p.numel() / 8 bytes");
+  TORCH_CHECK(step.is_cuda() && step.dtype() == torch::kInt32
+              && step.numel() == 1);
+  TORCH_CHECK(bf16_out.is_cuda() && bf16_out.dtype() == torch::kBFloat16
+              && bf16_out.is_contiguous() && bf16_out.numel() == p.numel());
+  long n4 = p.numel() / 4;
+  auto stream = at::cuda::getCurrentHIPStream();
+  hipLaunchKernelGGL((adamw_devstep_kernel<unsigned short, unsigned char>),
+                     dim3(grid_for(n4, 256)), dim3(256), 0, stream,
+                     p.data_ptr<float>(),
+                     (const unsigned short*)g.data_ptr(), (float)gmul,
+                     m.data_ptr<float>(), v.data_ptr<float>(),
+                     wd_bits.data_ptr<unsigned char>(), step.data_ptr<int>(),
+                     (unsigned short*)bf16_out.data_ptr(), gs_ptr, n4,
+                     (float)lr, (float)beta1, (float)beta2, (float)eps,
+                     (float)wd);
   HIP_CHECK_KERNEL();
 }
 
@@ -291,8 +302,33 @@ torch::Tensor multi_tensor_sqsum(std::vector<torch::Tensor> tensors) {
     TORCH_CHECK(t.is_cuda() && t.dtype() == torch::kFloat32
                 && t.is_contiguous() && t.numel() % 4 == 0);
     long n4 = t.numel() / 4;
-    hipLaunchKernelGGL(sqsum_kernel, dim3(grid_for(n4, 256)), dim3(256), 0,
-                       stream, t.data_ptr<float>(), n4, out.data_ptr<float>());
+    hipLaunchKernelGGL(sqsum_kernel<float>, dim3(grid_for(n4, 256)), dim3(256),
+                       0, stream, t.data_ptr<float>(), 1.0f, n4,
+                       out.data_ptr<float>());
+    HIP_CHECK_KERNEL();
+  }
+  return out;
+}
+
+// sum over every tensor of (float(g) * gmul)^2: the norm of pending bf16
+// gradients without their fp32 copy. numel % 8 as the AdamW that follows.
+torch::Tensor multi_tensor_sqsum_bf16(std::vector<torch::Tensor> tensors,
+                                      double gmul) {
+  TORCH_CHECK(!tensors.empty());
+  for (auto& t : tensors)
+    TORCH_CHECK(t.is_cuda() && t.dtype() == torch::kBFloat16
+                && t.is_contiguous() && t.numel() % 8 == 0
+                && t.device() == tensors[0].device(),
+                "multi_tensor_sqsum_bf16: tensors must be contiguous device "
+                "bf16 with numel % 8 == 0");
+  auto out = torch::zeros({}, tensors[0].options().dtype(torch::kFloat32));
+  auto stream = at::cuda::getCurrentHIPStream();
+  for (auto& t : tensors) {
+    long n4 = t.numel() / 4;
+    hipLaunchKernelGGL(sqsum_kernel<unsigned short>, dim3(grid_for(n4, 256)),
+                       dim3(256), 0, stream,
+                       (const unsigned short*)t.data_ptr(), (float)gmul, n4,
+                       out.data_ptr<float>());
     HIP_CHECK_KERNEL();
   }
   return out;

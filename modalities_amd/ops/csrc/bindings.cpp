@@ -45,6 +45,15 @@ void fused_adamw(std::vector<torch::Tensor> ps, std::vector<torch::Tensor> gs,
                  double lr, double beta1, double beta2, double eps, double wd,
                  double bc1, double bc2);
 torch::Tensor multi_tensor_sqsum(std::vector<torch::Tensor> tensors);
+void fused_adamw_devstep_bf16g(torch::Tensor p, torch::Tensor g, double gmul,
+                               torch::Tensor m, torch::Tensor v,
+                               torch::Tensor wd_bits, torch::Tensor step,
+                               torch::Tensor bf16_out,
+                               c10::optional<torch::Tensor> gscale, double lr,
+                               double beta1, double beta2, double eps,
+                               double wd);
+torch::Tensor multi_tensor_sqsum_bf16(std::vector<torch::Tensor> tensors,
+                                      double gmul);
 void multi_tensor_scale(std::vector<torch::Tensor> tensors, torch::Tensor scale);
 std::vector<torch::Tensor> attn_fwd(torch::Tensor q, torch::Tensor k,
                                     torch::Tensor v, bool causal,
@@ -152,6 +161,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("fused_adamw_masked_devstep", &fused_adamw_masked_devstep,
         "AdamW with device-resident step counter (hipGraph-safe)");
   m.def("multi_tensor_sqsum", &multi_tensor_sqsum, "sum of squares (K10)");
+  m.def("fused_adamw_devstep_bf16g", &fused_adamw_devstep_bf16g,
+        "device-step AdamW reading a bf16 grad (* gmul) and a bit-packed "
+        "decay mask (K9)");
+  m.def("multi_tensor_sqsum_bf16", &multi_tensor_sqsum_bf16,
+        "sum of squares of float(bf16) * gmul (K10)");
   m.def("multi_tensor_scale", &multi_tensor_scale, "in-place scale (K10)");
   m.def("attn_fwd",
         [](torch::Tensor q, torch::Tensor k, torch::Tensor v, bool causal,

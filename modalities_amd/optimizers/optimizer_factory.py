@@ -18,6 +18,10 @@ class ShardedAdamW(torch.optim.Optimizer):
     - exp_avg / exp_avg_sq are fp32 shards (persisted in state for DCP).
     - weight decay is applied through each unit's wd_mask_shard so norm/bias
       elements get 0 decay inside the flat shard.
+    - a unit whose reduced gradient is still pending in bf16 (one
+      micro-batch per step) is stepped by the kernel that reads the bf16
+      gradient in place and the mask as one bit per element; every other
+      unit takes the fp32 gradient shard and the fp32 mask. Same bits.
     """
 
     def __init__(self, sharded_model: XGMIShardedModel, lr: float = 3e-4,
@@ -41,6 +45,27 @@ class ShardedAdamW(torch.optim.Optimizer):
         # would freeze at capture). Lazily initialized from the CPU step so
         # warmstart loads are honored.
         self._step_dev = None
+        # Bit-packed decay masks for the bf16-gradient kernel, one per unit
+        # that keeps its reduced gradient in bf16: (bits or None, the mask
+        # tensor they were built from, its version).
+        self._wd_bits = {}
+        for u in sharded_model.units:
+            if u.keep_bf16_grads:
+                self._wd_bits_for(u)
+
+    def _wd_bits_for(self, u):
+        """The unit's decay mask as one bit per element, or None where the
+        mask is not 0/1 (such a unit keeps the fp32 mask and kernel). Built
+        once; rebuilt when wd_mask_shard was written or replaced since — a
+        host-side integer compare per step."""
+        from modalities_amd.ops.adamw import pack_wd_bits
+        mask = u.wd_mask_shard
+        cached = self._wd_bits.get(u.name)
+        if cached is None or cached[1] is not mask \
+                or cached[2] != mask._version:
+            cached = (pack_wd_bits(mask), mask, mask._version)
+            self._wd_bits[u.name] = cached
+        return cached[0]
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -79,8 +104,22 @@ class ShardedAdamW(torch.optim.Optimizer):
             st["step"] += 1
             step = st["step"]
             m, v = st["exp_avg"], st["exp_avg_sq"]
-            g = u.grad_shard
             p = u.master_shard
+            bits = self._wd_bits_for(u) if on_gpu \
+                and u._pending_grad is not None else None
+            if bits is not None:
+                # single micro-batch: the kernel reads the reduced bf16
+                # gradient in place (no fp32 copy) and one mask bit per
+                # element; same arithmetic, same bits as the branch below
+                hip_ext().fused_adamw_devstep_bf16g(
+                    p, u._pending_grad, u._pending_gmul, m, v, bits,
+                    self._step_dev, u.bf16_shard, gscale, lr, beta1, beta2,
+                    eps, wd)
+                if u.full_buf is not None and self.sharded_model.world > 1:
+                    u.free_full()  # stale gathered params
+                self.sharded_model.prefetch_unit_gather(ui)
+                continue
+            g = u.grad_shard  # materializes a pending bf16 gradient
             if on_gpu and u.bf16_shard.dtype == torch.bfloat16:
                 # fused publish: the kernel writes the bf16 working shard in
                 # the same pass (saves a full param re-read + cast)

@@ -10,8 +10,14 @@ for the MI355X node topology:
   bucketed RCCL all-gather per group ("big shards, few large collectives" —
   xGMI is 7 point-to-point links x ~153 GB/s, so per-message efficiency
   matters more than on a switched fabric).
-- Gradients reduce-scatter in bf16 into persistent fp32 shard accumulators
-  (grad accumulation sums in fp32).
+- Gradients reduce-scatter in bf16. With one micro-batch per step (bf16
+  params on the GPU) the reduced bf16 gradient stays where the collective
+  left it, "pending", and the norm and AdamW kernels read it in place:
+  bf16 -> fp32 is exact, so no fp32 copy is made. Anything that reads
+  `grad_shard` (a second micro-batch, HSDP/CP all-reduces, callers) first
+  materializes it into the persistent fp32 shard accumulator, where grad
+  accumulation sums in fp32. MODALITIES_AMD_BF16_GRAD_PATH=0 materializes
+  at reduce time instead (A/B runs, equivalence tests).
 - 288 GB HBM3E per GPU means models <= ~10B can keep ALL bf16 params resident
   for the whole step (`reshard_after_forward=False` default): backward needs
   no re-gathers at all; each step costs exactly one all-gather and one
@@ -29,6 +35,7 @@ CPU/gloo fallback (tests): gloo has no reduce_scatter, so it is emulated with
 all_reduce + local slice; streams collapse to synchronous calls.
 """
 
+import os
 import re
 from contextlib import contextmanager
 from typing import Optional
@@ -107,8 +114,17 @@ class FlatParamUnit:
         self.master_shard = torch.zeros(self.shard_numel, dtype=torch.float32, device=device)
         # grad_shard carries no valid data until the first reduce of a step
         # OVERWRITES it (grad_fresh flag) — avoids a full fp32 fill per step.
-        self.grad_shard = torch.empty(self.shard_numel, dtype=torch.float32, device=device)
+        self._grad_shard_f32 = torch.empty(self.shard_numel, dtype=torch.float32,
+                                           device=device)
         self.grad_fresh = False  # True once this step's first reduce landed
+        # The step's first reduce result, kept in bf16 until something needs
+        # fp32 (see grad_shard); its value is float(_pending_grad) *
+        # _pending_gmul. Only with bf16 params on the GPU.
+        self.keep_bf16_grads = (
+            device.type == "cuda" and param_dtype == torch.bfloat16
+            and os.environ.get("MODALITIES_AMD_BF16_GRAD_PATH", "1") != "0")
+        self._pending_grad: Optional[torch.Tensor] = None
+        self._pending_gmul = 1.0
         self.bf16_shard = torch.zeros(self.shard_numel, dtype=param_dtype, device=device)
         self.full_buf: Optional[torch.Tensor] = None
         self.grad_full: Optional[torch.Tensor] = None
@@ -117,6 +133,31 @@ class FlatParamUnit:
         self.grads_seen = 0
         self._gather_event = None
         self._reduce_event = None
+
+    # -- gradients -------------------------------------------------------
+
+    @property
+    def grad_shard(self) -> torch.Tensor:
+        """The fp32 gradient shard. A pending bf16 gradient is first written
+        into it, with the copy_ and mul_ a reduce without the bf16 path
+        does, and dropped."""
+        self.materialize_grad()
+        return self._grad_shard_f32
+
+    @grad_shard.setter
+    def grad_shard(self, value: torch.Tensor):
+        self._pending_grad = None
+        self._grad_shard_f32 = value
+
+    @torch.no_grad()
+    def materialize_grad(self):
+        out = self._pending_grad
+        if out is None:
+            return
+        self._pending_grad = None
+        self._grad_shard_f32.copy_(out)
+        if self._pending_gmul != 1.0:
+            self._grad_shard_f32.mul_(self._pending_gmul)
 
     # -- init ------------------------------------------------------------
 
@@ -194,12 +235,23 @@ class FlatParamUnit:
         self.grads_allocated = True
 
     def reduce_scatter_grads(self, streams: _CommStreams):
-        """Reduce-scatter bf16 grads (mean over DP) into the fp32 shard."""
+        """Reduce-scatter bf16 grads (mean over DP): the step's first result
+        stays pending in bf16 (or overwrites the fp32 shard without the bf16
+        path), later ones add into the fp32 shard."""
         gf = self.grad_full
         if gf is None:
             return
+        compute = torch.cuda.current_stream(self.device) if streams.on_gpu \
+            else None
         with streams.on(streams.reduce):
             if streams.on_gpu:
+                # KNOWN ISSUE, kept as it was: inside this context the
+                # current stream IS the reduce stream, so this does not
+                # order the reduce stream after the backward. A pending
+                # gradient at world 1 is not affected (nothing runs on the
+                # reduce stream, it is read on the compute stream); the
+                # collective and the fp32 materialization below are
+                # (measured in profiles/optimizer_tail_bf16.md).
                 streams.reduce.wait_stream(torch.cuda.current_stream(self.device))
             if self.world > 1:
                 backend = dist.get_backend(self.group) if self.group is not None \
@@ -216,11 +268,17 @@ class FlatParamUnit:
                 out = gf
             scale = 1.0 / self.world
             if self.grad_fresh:
+                # (a pending first result materializes here, on this stream)
                 self.grad_shard.add_(out, alpha=scale)
             else:  # first reduce of the step overwrites (grad_shard is stale)
-                self.grad_shard.copy_(out)
-                if scale != 1.0:
-                    self.grad_shard.mul_(scale)
+                self._pending_grad, self._pending_gmul = out, scale
+                if self.keep_bf16_grads:
+                    if out is not gf:
+                        # allocated on the reduce stream, read by the norm
+                        # and AdamW kernels on the compute stream
+                        out.record_stream(compute)
+                else:
+                    self.materialize_grad()
                 self.grad_fresh = True
             if streams.on_gpu:
                 self._reduce_event = torch.cuda.Event()
@@ -463,14 +521,16 @@ class XGMIShardedModel(nn.Module):
         if self._replicate_group is not None:
             ws = dist.get_world_size(self._replicate_group)
             for u in self.units:
-                dist.all_reduce(u.grad_shard, group=self._replicate_group)
-                u.grad_shard.div_(ws)
+                g = u.grad_shard  # materializes a pending bf16 gradient
+                dist.all_reduce(g, group=self._replicate_group)
+                g.div_(ws)
 
     @torch.no_grad()
     def zero_grad_shards(self):
         # no fill: the next step's first reduce overwrites (grad_fresh)
         for u in self.units:
             u.grad_fresh = False
+            u._pending_grad = None
 
     @torch.no_grad()
     def publish_master(self):
@@ -509,8 +569,24 @@ class XGMIShardedModel(nn.Module):
         (reference fsdp_gradient_clipper.py:166-169) — each rank then clips
         by the MODEL-global norm, and the published value is global."""
         from modalities_amd.ops.adamw import multi_tensor_l2norm, multi_tensor_scale_
-        fresh = [u.grad_shard for u in self.units if u.grad_fresh]
-        local = multi_tensor_l2norm(fresh) ** 2
+        units = [u for u in self.units if u.grad_fresh]
+        clipping = max_norm is not None and max_norm > 0
+        defer = getattr(self, "_optimizer_consumes_grad_scale", False)
+        if clipping and not defer:
+            for u in units:  # scaled in place below: that needs fp32
+                u.materialize_grad()
+        # pending bf16 gradients are summed where they lie
+        pending = [u for u in units if u._pending_grad is not None]
+        fresh = [u.grad_shard for u in units if u._pending_grad is None]
+        if pending:
+            from modalities_amd.ops.backend import hip_ext
+            # one 1/world factor for every unit of this engine
+            local = hip_ext().multi_tensor_sqsum_bf16(
+                [u._pending_grad for u in pending], pending[0]._pending_gmul)
+            if fresh:
+                local = local + multi_tensor_l2norm(fresh) ** 2
+        else:
+            local = multi_tensor_l2norm(fresh) ** 2
         if local.device != torch.device(self.device):
             local = local.to(self.device)
         if self.world > 1:
@@ -518,10 +594,9 @@ class XGMIShardedModel(nn.Module):
         if pp_group is not None:
             dist.all_reduce(local, group=pp_group)
         total = local.sqrt()
-        if max_norm is not None and max_norm > 0 and fresh:
+        if clipping and units:
             clip = (max_norm / (total + 1e-6)).clamp(max=1.0)
-            if getattr(self, "_optimizer_consumes_grad_scale", False) \
-                    and total.is_cuda:
+            if defer and total.is_cuda:
                 # ShardedAdamW folds the clip coefficient into its fused
                 # kernel's grad read — deferring skips a full read+write
                 # pass over every grad shard here.
