@@ -179,7 +179,8 @@ def _build_text_inference_component(config_path: Path):
         device=torch.device(settings.device),
         sample_key=settings.referencing_keys.get("sample_key", "input_ids"),
         prediction_key=settings.referencing_keys.get("prediction_key", "logits"),
-        use_decode_graph=gen_cfg.get("use_decode_graph", True))
+        use_decode_graph=gen_cfg.get("use_decode_graph", True),
+        decode_weight_format=gen_cfg.get("decode_weight_format"))
     return comp
 
 

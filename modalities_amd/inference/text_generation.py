@@ -10,7 +10,12 @@ With a KV cache on the GPU, the per-token decode step reads its position
 from device counters (KVCache.pos_dev), so after the prefill one step is
 captured into a hipGraph (`DecodeGraph`) and replayed per token: the eager
 launch chain of a step is paid once. `use_decode_graph=False` opts out; a
-capture that fails falls back to the eager step."""
+capture that fails falls back to the eager step.
+
+`decode_weight_format` ("fp8_e4m3" or "bf16"; default None = off) has the
+model build its decode weights (GPT2LLM.prepare_decode_weights) before the
+prefill: the single-token steps, captured or eager, then run their linears
+through the in-tree skinny GEMM, on weight-only FP8 for "fp8_e4m3"."""
 
 import sys
 from typing import Optional
@@ -93,7 +98,13 @@ class TextInferenceComponent:
                  eod_token: str = "<eod>", device: Optional[torch.device] = None,
                  sample_key: str = "input_ids", prediction_key: str = "logits",
                  top_k: Optional[int] = None, top_p: Optional[float] = None,
-                 use_decode_graph: bool = True):
+                 use_decode_graph: bool = True,
+                 decode_weight_format: Optional[str] = None):
+        if decode_weight_format is not None \
+                and not hasattr(model, "prepare_decode_weights"):
+            raise ValueError(
+                f"decode_weight_format={decode_weight_format!r}: "
+                f"{type(model).__name__} has no prepare_decode_weights")
         self.model = model
         self.tokenizer = tokenizer
         self.prompt_template = prompt_template
@@ -106,6 +117,7 @@ class TextInferenceComponent:
         self.top_k = top_k
         self.top_p = top_p
         self.use_decode_graph = use_decode_graph
+        self.decode_weight_format = decode_weight_format
 
     def _sample(self, logits: torch.Tensor) -> torch.Tensor:
         """Greedy (temperature==0) or temperature sampling with optional
@@ -145,6 +157,10 @@ class TextInferenceComponent:
         generated: list[int] = []
         max_new = max(0, self.sequence_length - input_ids.shape[1])
         self.model.eval()
+        if self.decode_weight_format is not None and getattr(
+                self.model, "decode_weight_format",
+                None) != self.decode_weight_format:
+            self.model.prepare_decode_weights(self.decode_weight_format)
 
         # KV-cache incremental decode when the model supports it (GPT2LLM);
         # fall back to full-context re-forward otherwise.

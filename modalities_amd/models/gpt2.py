@@ -25,6 +25,9 @@ from modalities_amd.ops.attention import (DECODE_HEAD_DIMS, _doc_visible,
                                           decode_rope_append, document_starts,
                                           fused_qkv_rope_attention)
 from modalities_amd.ops.backend import use_hip
+from modalities_amd.ops.decode_linear import (DECODE_WEIGHT_FORMATS,
+                                              prepare_linear, set_prepared,
+                                              skinny_eligible, step_linear)
 from modalities_amd.ops.layer_norm import LayerNorm
 from modalities_amd.ops.linear import TwoStreamLinear
 from modalities_amd.ops.rms_norm import RMSNorm
@@ -134,6 +137,10 @@ def refuse_document_masking(model, what: str) -> None:
             "turn the flag off or run without it")
 
 
+def _call_linear(lin, x):
+    return lin(x)
+
+
 class CausalSelfAttention(nn.Module):
     """Separate q/k/v projections (GQA), fused RoPE, optional QK-norm, flash
     attention via K1 (no KV-head repetition on device)."""
@@ -232,11 +239,14 @@ class CausalSelfAttention(nn.Module):
             return self._forward_decode(x, rope_cos, rope_sin, cache_k,
                                         cache_v, *dec)
         kv_dim = self.head_dim * self.n_head_kv
+        # a single-token step takes the prepared decode weights, if any
+        lin = step_linear if T == 1 else _call_linear
         if self.fused_qkv:
-            qkv = self.qkv_attn(x)
+            qkv = lin(self.qkv_attn, x)
             q, k, v = qkv.split([C, kv_dim, kv_dim], dim=-1)
         else:
-            q, k, v = self.q_attn(x), self.k_attn(x), self.v_attn(x)
+            q, k, v = (lin(self.q_attn, x), lin(self.k_attn, x),
+                       lin(self.v_attn, x))
         q = q.view(B, T, self.n_head_q, self.head_dim)
         k = k.view(B, T, self.n_head_kv, self.head_dim)
         v = v.view(B, T, self.n_head_kv, self.head_dim)
@@ -265,7 +275,7 @@ class CausalSelfAttention(nn.Module):
             y = torch.nn.functional.scaled_dot_product_attention(
                 qt, kt, vt, attn_mask=mask)
             y = y.transpose(1, 2)
-        return self.c_proj(y.reshape(B, T, C))
+        return lin(self.c_proj, y.reshape(B, T, C))
 
     def _forward_decode(self, x, rope_cos, rope_sin, cache_k, cache_v,
                         pos_dev, lens_dev):
@@ -273,10 +283,12 @@ class CausalSelfAttention(nn.Module):
         kv_dim = self.head_dim * self.n_head_kv
         if self.fused_qkv:
             # q, k, v stay row-strided views into the joint projection
-            qkv = self.qkv_attn(x)
+            qkv = step_linear(self.qkv_attn, x)
             q, k, v = qkv.split([C, kv_dim, kv_dim], dim=-1)
         else:
-            q, k, v = self.q_attn(x), self.k_attn(x), self.v_attn(x)
+            q, k, v = (step_linear(self.q_attn, x),
+                       step_linear(self.k_attn, x),
+                       step_linear(self.v_attn, x))
         q = q.view(B, 1, self.n_head_q, self.head_dim)
         k = k.view(B, 1, self.n_head_kv, self.head_dim)
         v = v.view(B, 1, self.n_head_kv, self.head_dim)
@@ -286,7 +298,7 @@ class CausalSelfAttention(nn.Module):
         q = decode_rope_append(q, k, v, rope_cos, rope_sin, pos_dev,
                                cache_k, cache_v)
         y = decode_attention(q, cache_k, cache_v, lens_dev)
-        return self.c_proj(y.reshape(B, 1, C))
+        return step_linear(self.c_proj, y.reshape(B, 1, C))
 
     def _attend(self, q, k, v, doc_start=None):
         if self.attention_impl == AttentionImplementation.HIP_FLASH:
@@ -327,6 +339,11 @@ class TransformerMLP(nn.Module):
     def forward(self, x):
         return self.dropout(self.c_proj(self.gelu(self.c_fc(x))))
 
+    def forward_step(self, x):
+        """forward for a single-token decode step (inference: no dropout),
+        on the prepared decode weights where the linears carry them."""
+        return step_linear(self.c_proj, self.gelu(step_linear(self.c_fc, x)))
+
 
 class GPT2Block(nn.Module):
     """Pre-norm transformer block: x + attn(norm(x)); x + mlp(norm(x))."""
@@ -344,6 +361,9 @@ class GPT2Block(nn.Module):
                               packed=cfg.packed_swiglu)
         else:
             self.mlp = TransformerMLP(cfg.n_embd, cfg.ffn_hidden, cfg.bias, cfg.dropout)
+        # set by GPT2LLM.prepare_decode_weights: single-token steps then run
+        # the MLP on its prepared weights
+        self.decode_weights = False
 
     def forward(self, x, rope_cos, rope_sin, doc_start=None):
         if doc_start is None:
@@ -363,7 +383,10 @@ class GPT2Block(nn.Module):
             x = x + self.attn.forward_cached(self.attention_norm(x), rope_cos,
                                              rope_sin, cache_k, cache_v, pos,
                                              dec=dec)
-        x = x + self.mlp(self.ffn_norm(x))
+        if self.decode_weights and x.shape[1] == 1:
+            x = x + self.mlp.forward_step(self.ffn_norm(x))
+        else:
+            x = x + self.mlp(self.ffn_norm(x))
         return x
 
 
@@ -396,6 +419,7 @@ class GPT2LLM(NNModel):
             self.lm_head.weight = self.wte.weight
 
         self._rope_cache: Optional[tuple[torch.Tensor, torch.Tensor]] = None
+        self.decode_weight_format: Optional[str] = None
 
     # -- rope table ------------------------------------------------------
     def _rope(self, T: int, device):
@@ -473,6 +497,8 @@ class GPT2LLM(NNModel):
         cache.pos = pos + T
         cache.pos_dev.fill_(cache.pos)
         x = self.lm_head_norm(x)
+        if T == 1:
+            return {self.prediction_key: step_linear(self.lm_head, x)}
         return {self.prediction_key: self.lm_head(x)}
 
     def _decode_route(self, input_ids) -> bool:
@@ -502,7 +528,85 @@ class GPT2LLM(NNModel):
         cache.pos_dev.add_(1)
         cache.pos += 1
         x = self.lm_head_norm(x)
-        return {self.prediction_key: self.lm_head(x)}
+        return {self.prediction_key: step_linear(self.lm_head, x)}
+
+    # -- decode weights (weight-only FP8 / in-tree skinny GEMM) -----------
+    def _decode_linears(self) -> list[nn.Linear]:
+        """Every Linear a single-token step runs."""
+        lins = []
+        for block in self.blocks:
+            attn, mlp = block.attn, block.mlp
+            if attn.fused_qkv:
+                lins.append(attn.qkv_attn)
+            else:
+                lins += [attn.q_attn, attn.k_attn, attn.v_attn]
+            lins.append(attn.c_proj)
+            if isinstance(mlp, SwiGLU):
+                lins += [mlp.Wv] if mlp.packed else [mlp.W, mlp.V]
+                lins.append(mlp.W_2)
+            else:
+                lins += [mlp.c_fc, mlp.c_proj]
+        lins.append(self.lm_head)
+        return lins
+
+    @torch.no_grad()
+    def prepare_decode_weights(self, fmt: str) -> None:
+        """Build the decode-time copy of every Linear a single-token step
+        runs: `fmt` "fp8_e4m3" (per-row power-of-two scaled e4m3, half the
+        bytes) or "bf16" (the resident weight, for the in-tree kernel at
+        equal bytes). Single-token steps of `forward_cached` with a batch of
+        at most 8 then run these layers through `ops.skinny_linear`; a layer
+        whose in_features is no multiple of 16 keeps F.linear. Prefill,
+        `forward`, training and the state dict are untouched.
+
+        The bf16 weights stay resident (prefill needs them), so "fp8_e4m3"
+        adds half the linears' bf16 bytes to the model's footprint. Call it
+        on the device and in the dtype the model decodes in; `train()`,
+        `load_state_dict` and `clear_decode_weights` drop the copies."""
+        if fmt not in DECODE_WEIGHT_FORMATS:
+            raise ValueError(f"decode weight format must be one of "
+                             f"{DECODE_WEIGHT_FORMATS}, got {fmt!r}")
+        wrapped = [m for block in self.blocks for m in (block.attn, block.mlp)
+                   if "forward" in m.__dict__]
+        if wrapped or "forward" in self.wte.__dict__ \
+                or hasattr(self, "_tp_vocab_info"):
+            raise NotImplementedError(
+                "prepare_decode_weights: this model's linears are sharded "
+                "(tensor or context parallelism replaced the block "
+                "forwards); decode weights are built for whole linears only.")
+        lins = self._decode_linears()
+        for lin in lins:
+            if tuple(lin.weight.shape) != (lin.out_features, lin.in_features):
+                raise NotImplementedError(
+                    "prepare_decode_weights: the parameters are held by a "
+                    "sharding engine (a linear's weight is not resident in "
+                    "full); prepare the plain model instead.")
+        self.clear_decode_weights()
+        for lin in lins:
+            if skinny_eligible(lin.in_features):
+                set_prepared(lin, prepare_linear(lin.weight, lin.bias, fmt))
+        for block in self.blocks:
+            block.decode_weights = True
+        self.decode_weight_format = fmt
+
+    def clear_decode_weights(self) -> None:
+        """Drop the prepared decode weights: every step is back on the bf16
+        weights and the kernels it used before."""
+        for lin in self._decode_linears():
+            set_prepared(lin, None)
+        for block in self.blocks:
+            block.decode_weights = False
+        self.decode_weight_format = None
+
+    def train(self, mode: bool = True):
+        if mode and getattr(self, "decode_weight_format", None) is not None:
+            self.clear_decode_weights()   # they would go stale
+        return super().train(mode)
+
+    def load_state_dict(self, *args, **kwargs):
+        if getattr(self, "decode_weight_format", None) is not None:
+            self.clear_decode_weights()
+        return super().load_state_dict(*args, **kwargs)
 
 
 class KVCache:

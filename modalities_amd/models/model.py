@@ -9,6 +9,7 @@ import torch.nn as nn
 
 from modalities_amd.batch import DatasetBatch, InferenceResultBatch
 from modalities_amd.ops import silu_mul, silu_mul_joint
+from modalities_amd.ops.decode_linear import step_linear
 from modalities_amd.ops.linear import TwoStreamLinear
 
 WeightDecayGroups = dict[str, list[str]]
@@ -78,6 +79,15 @@ class SwiGLU(nn.Module):
         if self.packed:
             return self.W_2(silu_mul_joint(self.Wv(x)))
         return self.W_2(silu_mul(self.W(x), self.V(x)))
+
+    def forward_step(self, x: torch.Tensor) -> torch.Tensor:
+        """forward for a single-token decode step, on the prepared decode
+        weights (GPT2LLM.prepare_decode_weights) where the linears carry
+        them."""
+        if self.packed:
+            return step_linear(self.W_2, silu_mul_joint(step_linear(self.Wv, x)))
+        return step_linear(self.W_2, silu_mul(step_linear(self.W, x),
+                                              step_linear(self.V, x)))
 
 
 def model_predict_batch(model: nn.Module, batch: DatasetBatch) -> InferenceResultBatch:

@@ -8,6 +8,8 @@ torch SDPA/LayerNorm/CE/AdamW) with hand-written gfx950 HIP kernels:
                           optional per-document mask for packed sequences;
                           split-KV single-token decode over a KV cache with
                           a fused RoPE + cache append
+- K3  skinny_linear     : M <= 8 decode GEMM streaming bf16 or weight-only
+                          e4m3 weights straight to registers
 - K4  rope              : fused rotate-half RoPE on q,k
 - K5  rms_norm          : wave-level reduction norm fwd+bwd
 - K5  layer_norm        : register-resident row LayerNorm fwd+bwd (bf16)
@@ -40,3 +42,7 @@ from modalities_amd.ops.attention import (  # noqa: F401
     set_decode_attention,
 )
 from modalities_amd.ops.adamw import fused_adamw_step  # noqa: F401
+from modalities_amd.ops.decode_linear import (  # noqa: F401
+    quantize_weight_fp8,
+    skinny_linear,
+)

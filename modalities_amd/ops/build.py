@@ -27,6 +27,7 @@ SOURCES = [
     "attention_bwd.hip",
     "attention_v2.hip",
     "attention_decode.hip",
+    "decode_gemv.hip",
     "bindings.cpp",
 ]
 

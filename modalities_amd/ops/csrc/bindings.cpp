@@ -122,6 +122,10 @@ torch::Tensor decode_rope_append(torch::Tensor q, torch::Tensor k,
                                  c10::optional<torch::Tensor> sin_t,
                                  torch::Tensor pos, torch::Tensor k_cache,
                                  torch::Tensor v_cache);
+torch::Tensor skinny_linear(torch::Tensor x, torch::Tensor w,
+                            c10::optional<torch::Tensor> scale,
+                            c10::optional<torch::Tensor> bias);
+long skinny_linear_max_m();
 
 // v1/v2 dispatch: v2 (8-wave, 2 waves/SIMD) is the perf path; v1 kept for
 // A/B and as a fallback switch. Flip with set_attn_impl / MA_ATTN_IMPL.
@@ -292,4 +296,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("q"), py::arg("k"), py::arg("v"), py::arg("cos"),
         py::arg("sin"), py::arg("pos"), py::arg("k_cache"),
         py::arg("v_cache"));
+  // Skinny GEMM for single-token decoding (weight-only e4m3 or bf16).
+  m.def("skinny_linear", &skinny_linear,
+        "y [M,N] bf16 = x [M,K] bf16 . w [N,K]^T for 1 <= M <= 8, K % 16 == 0; "
+        "w is float8_e4m3fn with a per-row fp32 scale [N], or bf16 with "
+        "scale None; bias is bf16 [N] or None",
+        py::arg("x"), py::arg("w"), py::arg("scale") = py::none(),
+        py::arg("bias") = py::none());
+  m.def("skinny_linear_max_m", &skinny_linear_max_m,
+        "largest batch (rows of x) skinny_linear takes");
 }

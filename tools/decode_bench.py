@@ -3,12 +3,18 @@ re-forward on the flagship 2.7B shape (GPU).
 
     PYTHONPATH=. python tools/decode_bench.py [--ctx 512 2048 3968]
         [--batch 1] [--impl {flash,split,graph}]
+        [--weights {off,bf16,fp8_e4m3}]
 
 --impl picks the route of the cached single-token step: `flash` is the
 prefill kernel on the copied cache prefix (set_decode_attention(False)),
 `split` the split-KV decode kernels launched eagerly (the default of
 forward_cached), `graph` the same step captured into a hipGraph and replayed
 (the default of text generation).
+
+--weights picks the decode weights of the single-token steps: `off` (the
+default) leaves the linears on F.linear / hipBLASLt, `bf16` and `fp8_e4m3`
+prepare them (GPT2LLM.prepare_decode_weights) for the in-tree skinny GEMM,
+on the bf16 weights or on weight-only FP8.
 """
 
 import argparse
@@ -63,6 +69,27 @@ def time_cached(model, ids, iters, impl):
         set_decode_attention(True)
 
 
+def logit_error(model, ids):
+    """Logits of the first single-token step after a prefill of `ids`, on the
+    prepared decode weights against the same step on the bf16 weights."""
+    fmt = model.decode_weight_format
+
+    def step():
+        cache = model.new_kv_cache(ids.shape[0], max_len=ids.shape[1] + 8)
+        out = model.forward_cached({"input_ids": ids}, cache)["logits"]
+        nxt = out[:, -1:].argmax(-1)
+        return model.forward_cached({"input_ids": nxt},
+                                    cache)["logits"].float()
+
+    got = step()
+    model.clear_decode_weights()
+    ref = step()
+    model.prepare_decode_weights(fmt)
+    rel = ((got - ref).norm() / ref.norm()).item()
+    same = (got.argmax(-1) == ref.argmax(-1)).float().mean().item()
+    return rel, (got - ref).abs().max().item(), ref.abs().max().item(), same
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--ctx", type=int, nargs="+", default=[512, 2048, 3968])
@@ -70,18 +97,31 @@ def main():
     ap.add_argument("--batch", type=int, default=1)
     ap.add_argument("--impl", choices=["flash", "split", "graph"],
                     default="split")
+    ap.add_argument("--weights", choices=["off", "bf16", "fp8_e4m3"],
+                    default="off")
+    ap.add_argument("--logit-error", action="store_true",
+                    help="with --weights bf16/fp8_e4m3: also print the "
+                         "error of a step's logits against the bf16 route")
     ap.add_argument("--no-reforward", action="store_true",
                     help="skip the full-context re-forward comparison")
     args = ap.parse_args()
     model, cfg = build_model()
+    if args.weights != "off":
+        model.prepare_decode_weights(args.weights)
     for ctx in args.ctx:
         ids = torch.randint(0, cfg.vocab_size, (args.batch, ctx),
                             device="cuda")
         with torch.no_grad():
+            if args.logit_error and args.weights != "off":
+                rel, mx, top, same = logit_error(model, ids)
+                print(f"ctx {ctx}: logits {args.weights} vs bf16 route: "
+                      f"rel l2 {rel:.3e}, max abs {mx:.3e} (max |logit| "
+                      f"{top:.3f}), same argmax {same:.2f}")
             cached_ms = time_cached(model, ids, args.iters, args.impl)
             if args.no_reforward:
                 print(f"ctx {ctx}: cached {cached_ms:.2f} ms/tok  "
-                      f"[batch {args.batch}, {args.impl}]")
+                      f"[batch {args.batch}, {args.impl}, "
+                      f"weights {args.weights}]")
                 continue
 
             full = ids
@@ -95,8 +135,9 @@ def main():
                 out2 = model({"input_ids": full})
             torch.cuda.synchronize()
             refwd_ms = (time.time() - t0) / n_ref * 1000
-        tag = "" if (args.batch, args.impl) == (1, "split") \
-            else f"  [batch {args.batch}, {args.impl}]"
+        tag = "" if (args.batch, args.impl, args.weights) \
+            == (1, "split", "off") \
+            else f"  [batch {args.batch}, {args.impl}, weights {args.weights}]"
         print(f"ctx {ctx}: cached {cached_ms:.1f} ms/tok  "
               f"re-forward {refwd_ms:.1f} ms/tok  ({refwd_ms/cached_ms:.1f}x)"
               + tag)
