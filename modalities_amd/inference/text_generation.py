@@ -14,8 +14,10 @@ capture that fails falls back to the eager step.
 
 `decode_weight_format` ("fp8_e4m3" or "bf16"; default None = off) has the
 model build its decode weights (GPT2LLM.prepare_decode_weights) before the
-prefill: the single-token steps, captured or eager, then run their linears
-through the in-tree skinny GEMM, on weight-only FP8 for "fp8_e4m3"."""
+prefill: the single-token steps of a batch of at most 32, captured or eager,
+then run their linears through the in-tree skinny GEMMs (the VALU kernel up
+to batch 8, the MFMA kernel for batch 9..32), on weight-only FP8 for
+"fp8_e4m3"."""
 
 import sys
 from typing import Optional

@@ -555,8 +555,11 @@ class GPT2LLM(NNModel):
         runs: `fmt` "fp8_e4m3" (per-row power-of-two scaled e4m3, half the
         bytes) or "bf16" (the resident weight, for the in-tree kernel at
         equal bytes). Single-token steps of `forward_cached` with a batch of
-        at most 8 then run these layers through `ops.skinny_linear`; a layer
-        whose in_features is no multiple of 16 keeps F.linear. Prefill,
+        at most 32 then run these layers on the copies: through
+        `ops.skinny_linear` up to batch 8, through `ops.skinny_linear_mfma`
+        for batch 9..32 on the GPU; a layer whose in_features is no multiple
+        of 16, any larger batch, and a batch above 8 on the CPU keep
+        F.linear. Prefill,
         `forward`, training and the state dict are untouched.
 
         The bf16 weights stay resident (prefill needs them), so "fp8_e4m3"

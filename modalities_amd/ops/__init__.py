@@ -10,6 +10,8 @@ torch SDPA/LayerNorm/CE/AdamW) with hand-written gfx950 HIP kernels:
                           a fused RoPE + cache append
 - K3  skinny_linear     : M <= 8 decode GEMM streaming bf16 or weight-only
                           e4m3 weights straight to registers
+- K3  skinny_linear_mfma: the same for M <= 32 on the matrix cores (MFMA),
+                          e4m3 widened to bf16 in registers
 - K4  rope              : fused rotate-half RoPE on q,k
 - K5  rms_norm          : wave-level reduction norm fwd+bwd
 - K5  layer_norm        : register-resident row LayerNorm fwd+bwd (bf16)
@@ -44,5 +46,7 @@ from modalities_amd.ops.attention import (  # noqa: F401
 from modalities_amd.ops.adamw import fused_adamw_step  # noqa: F401
 from modalities_amd.ops.decode_linear import (  # noqa: F401
     quantize_weight_fp8,
+    set_decode_mfma_min_rows,
     skinny_linear,
+    skinny_linear_mfma,
 )

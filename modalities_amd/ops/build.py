@@ -28,6 +28,7 @@ SOURCES = [
     "attention_v2.hip",
     "attention_decode.hip",
     "decode_gemv.hip",
+    "decode_gemv_mfma.hip",
     "bindings.cpp",
 ]
 

@@ -126,6 +126,11 @@ torch::Tensor skinny_linear(torch::Tensor x, torch::Tensor w,
                             c10::optional<torch::Tensor> scale,
                             c10::optional<torch::Tensor> bias);
 long skinny_linear_max_m();
+torch::Tensor skinny_linear_mfma(torch::Tensor x, torch::Tensor w,
+                                 c10::optional<torch::Tensor> scale,
+                                 c10::optional<torch::Tensor> bias,
+                                 long rt, long ksplit);
+long skinny_linear_mfma_max_m();
 
 // v1/v2 dispatch: v2 (8-wave, 2 waves/SIMD) is the perf path; v1 kept for
 // A/B and as a fallback switch. Flip with set_attn_impl / MA_ATTN_IMPL.
@@ -305,4 +310,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("bias") = py::none());
   m.def("skinny_linear_max_m", &skinny_linear_max_m,
         "largest batch (rows of x) skinny_linear takes");
+  m.def("skinny_linear_mfma", &skinny_linear_mfma,
+        "skinny_linear's contract for 1 <= M <= 32, on the matrix cores; "
+        "rt / ksplit pick a tiling for A/B (0: the shipped one)",
+        py::arg("x"), py::arg("w"), py::arg("scale") = py::none(),
+        py::arg("bias") = py::none(), py::arg("rt") = 0,
+        py::arg("ksplit") = 0);
+  m.def("skinny_linear_mfma_max_m", &skinny_linear_mfma_max_m,
+        "largest batch (rows of x) skinny_linear_mfma takes");
 }

@@ -24,10 +24,21 @@ Arithmetic of `skinny_linear`: products and sums in fp32, then `* scale[n]`,
 torch fp32. bf16 weights (`scale=None`) go through the same kernel: the A/B
 of the in-tree kernel against hipBLASLt at equal bytes.
 
+`skinny_linear_mfma` (csrc/decode_gemv_mfma.hip) has the same contract for
+1 <= M <= 32 rows. It feeds the weight to the matrix cores (MFMA), so its
+arithmetic per weight does not grow with M; its sums are fp32 in another
+fixed order, so it agrees with `skinny_linear` to the rounding bound, not
+bit for bit.
+
 `PreparedLinear` / `step_linear` are what the model uses: a prepared copy of
-a Linear's weight, and the call that takes it for a single-token step.
+a Linear's weight, and the call that takes it for a single-token step: up to
+8 rows through `skinny_linear`, 9 to 32 (on the GPU) through
+`skinny_linear_mfma`.
+`set_decode_mfma_min_rows` / MA_DECODE_MFMA_MIN_M move that border down for
+A/B.
 """
 
+import os
 from typing import NamedTuple, Optional
 
 import torch
@@ -37,6 +48,13 @@ from modalities_amd.ops.backend import hip_ext, use_hip
 
 E4M3_MAX = 448.0
 SKINNY_MAX_M = 8
+SKINNY_MFMA_MAX_M = 32
+# skinny_linear_mfma: a workgroup owns 16 * RT weight rows. RT = 2 halves the
+# x bytes a workgroup pulls from L2 per weight byte and wins wherever it still
+# leaves this many workgroups (3/4 of the MI355X's 256 CUs; measured at N =
+# 7680: 240 workgroups, against N = 2560: 80, nothing in between;
+# profiles/decode_gemv.md).
+SKINNY_MFMA_FILL_WGS = 192
 SKINNY_K_MULTIPLE = 16
 DECODE_WEIGHT_FORMATS = ("fp8_e4m3", "bf16")
 
@@ -78,7 +96,7 @@ def quantize_weight_fp8(w: torch.Tensor,
     return wq, scale.contiguous()
 
 
-def _check_skinny_args(x, w, scale, bias):
+def _check_skinny_args(x, w, scale, bias, max_m=SKINNY_MAX_M):
     for name, t in (("x", x), ("w", w)):
         if not isinstance(t, torch.Tensor):
             raise TypeError(f"skinny_linear: {name} must be a tensor")
@@ -92,8 +110,8 @@ def _check_skinny_args(x, w, scale, bias):
                          f"{tuple(x.shape)} and {tuple(w.shape)}")
     M, K = x.shape
     N = w.shape[0]
-    if not 1 <= M <= SKINNY_MAX_M:
-        raise ValueError(f"skinny_linear: M must be in [1, {SKINNY_MAX_M}], "
+    if not 1 <= M <= max_m:
+        raise ValueError(f"skinny_linear: M must be in [1, {max_m}], "
                          f"got {M}")
     if w.shape[1] != K:
         raise ValueError(f"skinny_linear: x has K = {K}, w has K = "
@@ -161,6 +179,52 @@ def skinny_linear(x: torch.Tensor, w: torch.Tensor,
     return _skinny_linear_ref(x, w, scale, bias)
 
 
+def skinny_linear_mfma(x: torch.Tensor, w: torch.Tensor,
+                       scale: Optional[torch.Tensor] = None,
+                       bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`skinny_linear`'s contract for 1 <= M <= 32, on the matrix cores:
+    y [M, N] bf16 = x [M, K] . w [N, K]^T (* scale[n]) (+ bias[n]), fp32
+    products and sums, one rounding. A row's result does not depend on M or
+    on where the row sits in x. Against hipBLASLt on the bf16 weight
+    (2.7B shapes, profiles/decode_gemv.md): with e4m3 weights it wins at
+    M = 8 (1.11-1.73x) and M = 16 (1.10-1.53x; lm_head ties) and loses at
+    M = 32 (0.73-0.96x), where the x every workgroup reads from L2 outweighs
+    the halved weight bytes; with bf16 weights it loses at most shapes."""
+    _check_skinny_args(x, w, scale, bias, SKINNY_MFMA_MAX_M)
+    if use_hip(x, w, scale, bias):
+        if (x.shape[0] > 1 and x.stride(0) % 8 != 0) or x.data_ptr() % 16 != 0:
+            x = x.contiguous()   # the kernel reads x in 16-byte pieces
+        rt = 2 if -(-w.shape[0] // 32) >= SKINNY_MFMA_FILL_WGS else 1
+        return hip_ext().skinny_linear_mfma(x, w, scale, bias, rt)
+    return _skinny_linear_ref(x, w, scale, bias)
+
+
+def _env_min_rows() -> int:
+    n = int(os.environ.get("MA_DECODE_MFMA_MIN_M", SKINNY_MAX_M + 1))
+    if not 1 <= n <= SKINNY_MAX_M + 1:
+        raise ValueError(f"MA_DECODE_MFMA_MIN_M must be in [1, "
+                         f"{SKINNY_MAX_M + 1}], got {n}")
+    return n
+
+
+_MFMA_MIN_ROWS = _env_min_rows()
+
+
+def set_decode_mfma_min_rows(n: int) -> None:
+    """Smallest batch `step_linear` sends to `skinny_linear_mfma`: 9 (the
+    default) keeps batches of up to 8 on `skinny_linear`; 1..8 move them to
+    the MFMA kernel (A/B). MA_DECODE_MFMA_MIN_M sets the initial value."""
+    global _MFMA_MIN_ROWS
+    if not 1 <= int(n) <= SKINNY_MAX_M + 1:
+        raise ValueError(f"set_decode_mfma_min_rows: n must be in [1, "
+                         f"{SKINNY_MAX_M + 1}], got {n}")
+    _MFMA_MIN_ROWS = int(n)
+
+
+def decode_mfma_min_rows() -> int:
+    return _MFMA_MIN_ROWS
+
+
 class PreparedLinear(NamedTuple):
     """Decode-time copy of one Linear: w [N, K] in `fmt`, its scale (e4m3
     only) and the bias in bf16."""
@@ -207,17 +271,25 @@ def get_prepared(lin: torch.nn.Module) -> Optional[PreparedLinear]:
 
 
 def step_linear(lin: torch.nn.Module, x: torch.Tensor) -> torch.Tensor:
-    """`lin(x)` for a single-token step x [B, 1, K]: through `skinny_linear`
-    on the prepared weight when `lin` has one, B <= 8 and x is bf16 on the
-    weight's device; through the module itself (F.linear on the resident
-    weight) otherwise."""
+    """`lin(x)` for a single-token step x [B, 1, K]: on the prepared weight
+    when `lin` has one, B <= 32 and x is bf16 on the weight's device --
+    through `skinny_linear` for B <= 8, through `skinny_linear_mfma` for
+    9 <= B <= 32 (`set_decode_mfma_min_rows` moves the border down);
+    through the module itself (F.linear on the resident weight) otherwise.
+    The MFMA route is the device's: on the CPU, where there is no kernel to
+    reach, a step of more than 8 rows stays on F.linear as it always has."""
     prep = lin.__dict__.get(_ATTR)
     if prep is None:
         return lin(x)
     rows = x.numel() // x.shape[-1]
-    if rows > SKINNY_MAX_M or rows < 1 or x.dtype != torch.bfloat16 \
+    mfma = x.is_cuda and rows >= _MFMA_MIN_ROWS
+    max_rows = SKINNY_MFMA_MAX_M if mfma else SKINNY_MAX_M
+    if rows > max_rows or rows < 1 or x.dtype != torch.bfloat16 \
             or x.device != prep.w.device:
         return F.linear(x, lin.weight, lin.bias)
     x2 = x.reshape(rows, x.shape[-1])
-    y = skinny_linear(x2, prep.w, prep.scale, prep.bias)
+    if mfma:
+        y = skinny_linear_mfma(x2, prep.w, prep.scale, prep.bias)
+    else:
+        y = skinny_linear(x2, prep.w, prep.scale, prep.bias)
     return y.view(*x.shape[:-1], prep.w.shape[0])

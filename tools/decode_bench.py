@@ -2,7 +2,7 @@
 re-forward on the flagship 2.7B shape (GPU).
 
     PYTHONPATH=. python tools/decode_bench.py [--ctx 512 2048 3968]
-        [--batch 1] [--impl {flash,split,graph}]
+        [--batch 1 [16 32 ...]] [--impl {flash,split,graph}]
         [--weights {off,bf16,fp8_e4m3}]
 
 --impl picks the route of the cached single-token step: `flash` is the
@@ -13,8 +13,10 @@ forward_cached), `graph` the same step captured into a hipGraph and replayed
 
 --weights picks the decode weights of the single-token steps: `off` (the
 default) leaves the linears on F.linear / hipBLASLt, `bf16` and `fp8_e4m3`
-prepare them (GPT2LLM.prepare_decode_weights) for the in-tree skinny GEMM,
-on the bf16 weights or on weight-only FP8.
+prepare them (GPT2LLM.prepare_decode_weights) for the in-tree skinny GEMMs
+(the VALU kernel up to batch 8, the MFMA kernel for batch 9..32), on the bf16
+weights or on weight-only FP8. --batch takes one or more batch sizes; each
+runs every --ctx.
 """
 
 import argparse
@@ -94,7 +96,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--ctx", type=int, nargs="+", default=[512, 2048, 3968])
     ap.add_argument("--iters", type=int, default=32)
-    ap.add_argument("--batch", type=int, default=1)
+    ap.add_argument("--batch", type=int, nargs="+", default=[1])
     ap.add_argument("--impl", choices=["flash", "split", "graph"],
                     default="split")
     ap.add_argument("--weights", choices=["off", "bf16", "fp8_e4m3"],
@@ -108,39 +110,40 @@ def main():
     model, cfg = build_model()
     if args.weights != "off":
         model.prepare_decode_weights(args.weights)
-    for ctx in args.ctx:
-        ids = torch.randint(0, cfg.vocab_size, (args.batch, ctx),
-                            device="cuda")
-        with torch.no_grad():
-            if args.logit_error and args.weights != "off":
-                rel, mx, top, same = logit_error(model, ids)
-                print(f"ctx {ctx}: logits {args.weights} vs bf16 route: "
-                      f"rel l2 {rel:.3e}, max abs {mx:.3e} (max |logit| "
-                      f"{top:.3f}), same argmax {same:.2f}")
-            cached_ms = time_cached(model, ids, args.iters, args.impl)
-            if args.no_reforward:
-                print(f"ctx {ctx}: cached {cached_ms:.2f} ms/tok  "
-                      f"[batch {args.batch}, {args.impl}, "
-                      f"weights {args.weights}]")
-                continue
+    for batch in args.batch:
+        for ctx in args.ctx:
+            ids = torch.randint(0, cfg.vocab_size, (batch, ctx),
+                                device="cuda")
+            with torch.no_grad():
+                if args.logit_error and args.weights != "off":
+                    rel, mx, top, same = logit_error(model, ids)
+                    print(f"ctx {ctx}: logits {args.weights} vs bf16 route: "
+                          f"rel l2 {rel:.3e}, max abs {mx:.3e} (max |logit| "
+                          f"{top:.3f}), same argmax {same:.2f}")
+                cached_ms = time_cached(model, ids, args.iters, args.impl)
+                if args.no_reforward:
+                    print(f"ctx {ctx}: cached {cached_ms:.2f} ms/tok  "
+                          f"[batch {batch}, {args.impl}, "
+                          f"weights {args.weights}]")
+                    continue
 
-            full = ids
-            out2 = model({"input_ids": full})
-            torch.cuda.synchronize()
-            t0 = time.time()
-            n_ref = max(4, args.iters // 4)
-            for _ in range(n_ref):
-                nxt = out2["logits"][:, -1:].argmax(-1)
-                full = torch.cat([full, nxt], 1)
+                full = ids
                 out2 = model({"input_ids": full})
-            torch.cuda.synchronize()
-            refwd_ms = (time.time() - t0) / n_ref * 1000
-        tag = "" if (args.batch, args.impl, args.weights) \
-            == (1, "split", "off") \
-            else f"  [batch {args.batch}, {args.impl}, weights {args.weights}]"
-        print(f"ctx {ctx}: cached {cached_ms:.1f} ms/tok  "
-              f"re-forward {refwd_ms:.1f} ms/tok  ({refwd_ms/cached_ms:.1f}x)"
-              + tag)
+                torch.cuda.synchronize()
+                t0 = time.time()
+                n_ref = max(4, args.iters // 4)
+                for _ in range(n_ref):
+                    nxt = out2["logits"][:, -1:].argmax(-1)
+                    full = torch.cat([full, nxt], 1)
+                    out2 = model({"input_ids": full})
+                torch.cuda.synchronize()
+                refwd_ms = (time.time() - t0) / n_ref * 1000
+            tag = "" if (batch, args.impl, args.weights) \
+                == (1, "split", "off") \
+                else f"  [batch {batch}, {args.impl}, weights {args.weights}]"
+            print(f"ctx {ctx}: cached {cached_ms:.1f} ms/tok  "
+                  f"re-forward {refwd_ms:.1f} ms/tok  "
+                  f"({refwd_ms/cached_ms:.1f}x)" + tag)
 
 
 if __name__ == "__main__":

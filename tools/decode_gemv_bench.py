@@ -1,12 +1,17 @@
-"""Kernel-level A/B of the batch-1..8 decode GEMMs on the 2.7B shapes (GPU):
+"""Kernel-level A/B of the batch-1..32 decode GEMMs on the 2.7B shapes (GPU):
 
   blaslt  F.linear on the bf16 weight (hipBLASLt), what a decode step runs
           with `decode_weight_format` unset
   bf16    ops.skinny_linear on the same bf16 weight (in-tree kernel, equal
           bytes)
   e4m3    ops.skinny_linear on the weight-only FP8 copy (half the bytes)
+  mfma-bf16 / mfma-e4m3
+          ops.skinny_linear_mfma (matrix cores, M <= 32) on the same two
 
-for QKV, c_proj, packed W|V, W_2 and lm_head at M = 1 and 8, in one process.
+for QKV, c_proj, packed W|V, W_2 and lm_head at M = 1, 8, 16 and 32, in one
+process; the VALU kernel (bf16, e4m3) only where M <= 8. `--tilings` times
+the MFMA kernel's RT x KSPLIT instantiations on the e4m3 weight instead (the
+A/B behind the shipped MFMA_GEMV_RT / MFMA_GEMV_KSPLIT).
 
 A decode step streams every weight of the model once per token, so each
 weight arrives cold. To time that and not a cache-resident loop, every shape
@@ -15,11 +20,12 @@ gets enough copies of its weight that one format's set exceeds `--cold-mb`
 take consecutive copies. The calls of one implementation are captured into a
 hipGraph, as the decode step is, and the replay is timed with device events:
 the figure is time per call inside a replayed graph, launch gaps included.
-`--repeats` replays alternate between the three implementations; the table
+`--repeats` replays alternate between the implementations; the table
 gives the median and the min..max spread. GB/s counts the weight bytes only.
 
-    PYTHONPATH=. python tools/decode_gemv_bench.py [--m 1 8] [--repeats 7]
-        [--calls 64] [--cold-mb 768] [--only qkv c_proj wv w2 lm_head]
+    PYTHONPATH=. python tools/decode_gemv_bench.py [--m 1 8 16 32]
+        [--repeats 7] [--calls 64] [--cold-mb 768] [--tilings]
+        [--only qkv c_proj wv w2 lm_head]
 """
 
 import argparse
@@ -68,17 +74,22 @@ def replay_us(g, ncalls):
 
 
 def main():
-    from modalities_amd.ops import quantize_weight_fp8, skinny_linear
-    from modalities_amd.ops.backend import require_hip
+    from modalities_amd.ops import (quantize_weight_fp8, skinny_linear,
+                                    skinny_linear_mfma)
+    from modalities_amd.ops.backend import hip_ext, require_hip
+    from modalities_amd.ops.decode_linear import SKINNY_MAX_M
     require_hip("decode_gemv_bench")
     ap = argparse.ArgumentParser()
-    ap.add_argument("--m", type=int, nargs="+", default=[1, 8])
+    ap.add_argument("--m", type=int, nargs="+", default=[1, 8, 16, 32])
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--calls", type=int, default=64,
                     help="calls per timed graph replay (at least the number "
                          "of weight copies is used)")
     ap.add_argument("--cold-mb", type=int, default=768)
     ap.add_argument("--only", nargs="+", default=None)
+    ap.add_argument("--tilings", action="store_true",
+                    help="time skinny_linear_mfma's RT x KSPLIT variants on "
+                         "the e4m3 weight instead of the implementations")
     args = ap.parse_args()
     torch.manual_seed(0)
     print(f"# cold set >= {args.cold_mb} MB per format; time per call inside "
@@ -94,20 +105,32 @@ def main():
         w8 = [wq.clone() for _ in range(ncopy)]
         for M in args.m:
             x = torch.randn(M, K, device="cuda").bfloat16()
-            impls = {
-                "blaslt": lambda i: F.linear(x, wb[i % ncopy]),
-                "bf16": lambda i: skinny_linear(x, wb[i % ncopy]),
-                "e4m3": lambda i: skinny_linear(x, w8[i % ncopy], scale),
-            }
+            impls = {"blaslt": lambda i: F.linear(x, wb[i % ncopy])}
+            if args.tilings:
+                for rt in (1, 2):
+                    for ks in (4, 8):
+                        impls[f"rt{rt}ks{ks}"] = \
+                            lambda i, rt=rt, ks=ks: hip_ext().skinny_linear_mfma(
+                                x, w8[i % ncopy], scale, None, rt, ks)
+            else:
+                if M <= SKINNY_MAX_M:
+                    impls["bf16"] = lambda i: skinny_linear(x, wb[i % ncopy])
+                    impls["e4m3"] = lambda i: skinny_linear(x, w8[i % ncopy],
+                                                            scale)
+                impls["mfma-bf16"] = lambda i: skinny_linear_mfma(
+                    x, wb[i % ncopy])
+                impls["mfma-e4m3"] = lambda i: skinny_linear_mfma(
+                    x, w8[i % ncopy], scale)
             graphs = {k: capture(fn, ncalls) for k, fn in impls.items()}
             for g, _ in graphs.values():     # warm every graph once
                 replay_us(g, ncalls)
             # results must agree before a time means anything (the outputs
             # of a graph hold values only after a replay)
             ref = graphs["blaslt"][1][0].float()
-            d_bf = (graphs["bf16"][1][0].float() - ref).abs().max().item()
             ref8 = F.linear(x, (wq.float() * scale[:, None]).bfloat16()).float()
-            d_8 = (graphs["e4m3"][1][0].float() - ref8).abs().max().item()
+            diff = {k: (graphs[k][1][0].float()
+                        - (ref if k.endswith("bf16") else ref8)).abs().max()
+                    .item() for k in impls if k != "blaslt"}
             us = {k: [] for k in impls}
             for _ in range(args.repeats):    # alternate the implementations
                 for k, (g, _) in graphs.items():
@@ -116,12 +139,15 @@ def main():
             med = {}
             for k in impls:
                 med[k] = statistics.median(us[k])
-                nbytes = N * K * (1 if k == "e4m3" else 2)
+                nbytes = N * K * (2 if k in ("blaslt", "bf16", "mfma-bf16")
+                                  else 1)
                 line += (f"  {k} {med[k]:7.2f} us [{min(us[k]):.2f}.."
                          f"{max(us[k]):.2f}] {nbytes / med[k] / 1e3:6.0f} GB/s")
-            line += (f"  | blaslt/bf16 {med['blaslt'] / med['bf16']:.2f}x "
-                     f"blaslt/e4m3 {med['blaslt'] / med['e4m3']:.2f}x "
-                     f"| maxdiff bf16 {d_bf:.1e} e4m3 {d_8:.1e}")
+            line += "  |" + "".join(
+                f" blaslt/{k} {med['blaslt'] / med[k]:.2f}x"
+                for k in impls if k != "blaslt")
+            line += "  | maxdiff" + "".join(f" {k} {d:.1e}"
+                                            for k, d in diff.items())
             print(line, flush=True)
             del graphs
         del wb, w8
