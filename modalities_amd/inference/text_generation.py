@@ -17,7 +17,13 @@ model build its decode weights (GPT2LLM.prepare_decode_weights) before the
 prefill: the single-token steps of a batch of at most 32, captured or eager,
 then run their linears through the in-tree skinny GEMMs (the VALU kernel up
 to batch 8, the MFMA kernel for batch 9..32), on weight-only FP8 for
-"fp8_e4m3"."""
+"fp8_e4m3".
+
+`kv_cache_format` ("fp8_e4m3"; default None = a cache in the model's dtype)
+has the model allocate an e4m3 KV cache (GPT2LLM.new_kv_cache(kv_format=...)):
+0.5x + 4 bytes per cached row, read by the FP8 decode kernels; the prefill
+stores quantised. It pays where the cache, not the weights, is the traffic:
+large batch times long context (profiles/decode_attention.md)."""
 
 import sys
 from typing import Optional
@@ -101,12 +107,23 @@ class TextInferenceComponent:
                  sample_key: str = "input_ids", prediction_key: str = "logits",
                  top_k: Optional[int] = None, top_p: Optional[float] = None,
                  use_decode_graph: bool = True,
-                 decode_weight_format: Optional[str] = None):
+                 decode_weight_format: Optional[str] = None,
+                 kv_cache_format: Optional[str] = None):
         if decode_weight_format is not None \
                 and not hasattr(model, "prepare_decode_weights"):
             raise ValueError(
                 f"decode_weight_format={decode_weight_format!r}: "
                 f"{type(model).__name__} has no prepare_decode_weights")
+        if kv_cache_format is not None:
+            from modalities_amd.ops.attention import KV_CACHE_FORMATS
+            if kv_cache_format not in KV_CACHE_FORMATS:
+                raise ValueError(f"kv_cache_format must be None or one of "
+                                 f"{KV_CACHE_FORMATS}, got "
+                                 f"{kv_cache_format!r}")
+            if not hasattr(model, "new_kv_cache"):
+                raise ValueError(
+                    f"kv_cache_format={kv_cache_format!r}: "
+                    f"{type(model).__name__} has no KV cache")
         self.model = model
         self.tokenizer = tokenizer
         self.prompt_template = prompt_template
@@ -120,6 +137,7 @@ class TextInferenceComponent:
         self.top_p = top_p
         self.use_decode_graph = use_decode_graph
         self.decode_weight_format = decode_weight_format
+        self.kv_cache_format = kv_cache_format
 
     def _sample(self, logits: torch.Tensor) -> torch.Tensor:
         """Greedy (temperature==0) or temperature sampling with optional
@@ -168,8 +186,11 @@ class TextInferenceComponent:
         # fall back to full-context re-forward otherwise.
         cache = None
         if hasattr(self.model, "forward_cached") and                 hasattr(self.model, "new_kv_cache"):
+            kw = {} if self.kv_cache_format is None \
+                else {"kv_format": self.kv_cache_format}
             cache = self.model.new_kv_cache(input_ids.shape[0],
-                                            max_len=self.sequence_length)
+                                            max_len=self.sequence_length,
+                                            **kw)
             out = self.model.forward_cached({self.sample_key: input_ids}, cache)
         else:
             out = self.model({self.sample_key: input_ids})

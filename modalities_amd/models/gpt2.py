@@ -19,11 +19,13 @@ from pydantic import BaseModel, Field, model_validator
 from modalities_amd.models.model import NNModel, SwiGLU
 from modalities_amd.ops import flash_attention, precompute_rope_cos_sin, rope_apply
 from modalities_amd.exceptions import ConfigError
-from modalities_amd.ops.attention import (DECODE_HEAD_DIMS, _doc_visible,
-                                          decode_attention,
+from modalities_amd.ops.attention import (DECODE_HEAD_DIMS, KV_CACHE_FORMATS,
+                                          _doc_visible, decode_attention,
                                           decode_attention_enabled,
-                                          decode_rope_append, document_starts,
-                                          fused_qkv_rope_attention)
+                                          decode_rope_append,
+                                          dequantize_kv_fp8, document_starts,
+                                          fused_qkv_rope_attention,
+                                          kv_quantize_store)
 from modalities_amd.ops.backend import use_hip
 from modalities_amd.ops.decode_linear import (DECODE_WEIGHT_FORMATS,
                                               prepare_linear, set_prepared,
@@ -221,7 +223,7 @@ class CausalSelfAttention(nn.Module):
         return self.resid_dropout(self.c_proj(y))
 
     def forward_cached(self, x, rope_cos, rope_sin, cache_k, cache_v,
-                       pos: int, dec=None):
+                       pos: int, dec=None, scales=None):
         """Incremental-decode step: project the T_new tokens at absolute
         positions [pos, pos+T_new), append K/V into the preallocated cache,
         attend q against the cache prefix with q_offset=pos (the same
@@ -232,10 +234,21 @@ class CausalSelfAttention(nn.Module):
         dec = (pos_dev, lens_dev), int32 [B] device tensors holding pos and
         pos + 1: a single-token step then takes the decode kernels, which
         read the position from the device (no host value in a launch
-        argument, no slicing, no copy of the cache prefix)."""
+        argument, no slicing, no copy of the cache prefix).
+
+        scales = (k_scale, v_scale) of an FP8 cache (cache_k / cache_v then
+        hold e4m3 codes). The decode kernels read the codes directly. Here,
+        off that route, K/V are quantised on store and de-quantised on
+        read: a prefill attends on its fresh bf16 K/V, a single token on the
+        cache including its own quantised row, and a chunk at pos > 0
+        de-quantises the whole prefix first -- a slow path, meant for
+        tests and the occasional chunked prefill, not for decoding."""
         B, T, C = x.shape
         if (dec is not None and T == 1
                 and self.attention_impl == AttentionImplementation.HIP_FLASH):
+            if scales is not None:
+                return self._forward_decode(x, rope_cos, rope_sin, cache_k,
+                                            cache_v, *dec, scales=scales)
             return self._forward_decode(x, rope_cos, rope_sin, cache_k,
                                         cache_v, *dec)
         kv_dim = self.head_dim * self.n_head_kv
@@ -257,10 +270,22 @@ class CausalSelfAttention(nn.Module):
             cos, sin = rope_cos[pos:pos + T], rope_sin[pos:pos + T]
             q = rope_apply(q, cos, sin)
             k = rope_apply(k, cos, sin)
-        cache_k[:, pos:pos + T] = k
-        cache_v[:, pos:pos + T] = v
-        k_full = cache_k[:, :pos + T]
-        v_full = cache_v[:, :pos + T]
+        if scales is None:
+            cache_k[:, pos:pos + T] = k
+            cache_v[:, pos:pos + T] = v
+            k_full = cache_k[:, :pos + T]
+            v_full = cache_v[:, :pos + T]
+        else:
+            kv_quantize_store(k, v, cache_k, cache_v, *scales, pos)
+            n = pos + 1 if T == 1 else pos   # cached rows attended to
+            if n == 0:
+                k_full, v_full = k, v
+            else:
+                k_full = dequantize_kv_fp8(cache_k[:, :n], scales[0][:, :n])
+                v_full = dequantize_kv_fp8(cache_v[:, :n], scales[1][:, :n])
+                if T > 1:
+                    k_full = torch.cat([k_full, k], dim=1)
+                    v_full = torch.cat([v_full, v], dim=1)
         if self.attention_impl == AttentionImplementation.HIP_FLASH and                 use_hip(q):
             y = flash_attention(q, k_full.contiguous(), v_full.contiguous(),
                                 causal=True, q_offset=pos)
@@ -278,7 +303,7 @@ class CausalSelfAttention(nn.Module):
         return lin(self.c_proj, y.reshape(B, T, C))
 
     def _forward_decode(self, x, rope_cos, rope_sin, cache_k, cache_v,
-                        pos_dev, lens_dev):
+                        pos_dev, lens_dev, scales=None):
         B, _, C = x.shape
         kv_dim = self.head_dim * self.n_head_kv
         if self.fused_qkv:
@@ -295,9 +320,16 @@ class CausalSelfAttention(nn.Module):
         if self.q_norm is not None:
             q = self.q_norm(q)
             k = self.k_norm(k)
-        q = decode_rope_append(q, k, v, rope_cos, rope_sin, pos_dev,
-                               cache_k, cache_v)
-        y = decode_attention(q, cache_k, cache_v, lens_dev)
+        if scales is None:
+            q = decode_rope_append(q, k, v, rope_cos, rope_sin, pos_dev,
+                                   cache_k, cache_v)
+            y = decode_attention(q, cache_k, cache_v, lens_dev)
+        else:
+            q = decode_rope_append(q, k, v, rope_cos, rope_sin, pos_dev,
+                                   cache_k, cache_v, k_scale=scales[0],
+                                   v_scale=scales[1])
+            y = decode_attention(q, cache_k, cache_v, lens_dev,
+                                 k_scale=scales[0], v_scale=scales[1])
         return step_linear(self.c_proj, y.reshape(B, 1, C))
 
     def _attend(self, q, k, v, doc_start=None):
@@ -375,8 +407,12 @@ class GPT2Block(nn.Module):
         return x
 
     def forward_cached(self, x, rope_cos, rope_sin, cache_k, cache_v, pos,
-                       dec=None):
-        if dec is None:
+                       dec=None, scales=None):
+        if scales is not None:   # FP8 cache
+            x = x + self.attn.forward_cached(self.attention_norm(x), rope_cos,
+                                             rope_sin, cache_k, cache_v, pos,
+                                             dec=dec, scales=scales)
+        elif dec is None:
             x = x + self.attn.forward_cached(self.attention_norm(x), rope_cos,
                                              rope_sin, cache_k, cache_v, pos)
         else:
@@ -461,13 +497,30 @@ class GPT2LLM(NNModel):
 
     # -- incremental decoding (KV cache) --------------------------------
     def new_kv_cache(self, batch_size: int, max_len: Optional[int] = None,
-                     device=None, dtype=None) -> "KVCache":
+                     device=None, dtype=None,
+                     kv_format: Optional[str] = None) -> "KVCache":
+        """kv_format "fp8_e4m3": the cache holds e4m3 codes and per-(token,
+        kv head) scales (see KVCache), D + 4 bytes per row instead of 2 D;
+        single-token steps on the decode route read it with the FP8 decode
+        kernels. Orthogonal to `prepare_decode_weights`."""
         cfg = self.config
         max_len = max_len or cfg.sequence_length
         p = next(self.parameters())
+        if kv_format is not None and self._sharded_forwards():
+            raise NotImplementedError(
+                "new_kv_cache: an FP8 KV cache is not supported on a model "
+                "whose block forwards are sharded (tensor or context "
+                "parallelism); use the plain model or a bf16 cache.")
         return KVCache(cfg.n_layer, batch_size, max_len,
                        cfg.n_head_kv, cfg.n_embd // cfg.n_head_q,
-                       device or p.device, dtype or p.dtype)
+                       device or p.device, dtype or p.dtype,
+                       kv_format=kv_format)
+
+    def _sharded_forwards(self) -> bool:
+        wrapped = [m for block in self.blocks for m in (block.attn, block.mlp)
+                   if "forward" in m.__dict__]
+        return bool(wrapped) or "forward" in self.wte.__dict__ \
+            or hasattr(self, "_tp_vocab_info")
 
     @torch.no_grad()
     def forward_cached(self, inputs: dict[str, torch.Tensor],
@@ -493,7 +546,8 @@ class GPT2LLM(NNModel):
         rope_cos, rope_sin = self._rope(cache.max_len, x.device)
         for i, block in enumerate(self.blocks):
             x = block.forward_cached(x, rope_cos, rope_sin,
-                                     cache.k[i], cache.v[i], pos)
+                                     cache.k[i], cache.v[i], pos,
+                                     **cache.scales(i))
         cache.pos = pos + T
         cache.pos_dev.fill_(cache.pos)
         x = self.lm_head_norm(x)
@@ -524,7 +578,7 @@ class GPT2LLM(NNModel):
         for i, block in enumerate(self.blocks):
             x = block.forward_cached(x, rope_cos, rope_sin,
                                      cache.k[i], cache.v[i], cache.pos,
-                                     dec=dec)
+                                     dec=dec, **cache.scales(i))
         cache.pos_dev.add_(1)
         cache.pos += 1
         x = self.lm_head_norm(x)
@@ -569,10 +623,7 @@ class GPT2LLM(NNModel):
         if fmt not in DECODE_WEIGHT_FORMATS:
             raise ValueError(f"decode weight format must be one of "
                              f"{DECODE_WEIGHT_FORMATS}, got {fmt!r}")
-        wrapped = [m for block in self.blocks for m in (block.attn, block.mlp)
-                   if "forward" in m.__dict__]
-        if wrapped or "forward" in self.wte.__dict__ \
-                or hasattr(self, "_tp_vocab_info"):
+        if self._sharded_forwards():
             raise NotImplementedError(
                 "prepare_decode_weights: this model's linears are sharded "
                 "(tensor or context parallelism replaced the block "
@@ -618,12 +669,28 @@ class KVCache:
     `pos` is the host-side count of cached tokens; `pos_dev` (the same
     value per batch row) and `lens_dev` (pos + 1 during a decode step: the
     keys the new token attends to) are its int32 device mirrors, which the
-    decode kernels read so that a captured step can be replayed."""
+    decode kernels read so that a captured step can be replayed.
+
+    kv_format None: `k`, `v` hold [B, max_len, Hkv, D] tensors of `dtype`.
+    kv_format "fp8_e4m3": they hold float8_e4m3fn codes, and `k_scale`,
+    `v_scale` the fp32 [B, max_len, Hkv] power-of-two scales of
+    `ops.quantize_kv_fp8` (D + 4 bytes per row; `dtype` is not used)."""
 
     def __init__(self, n_layer: int, batch_size: int, max_len: int,
-                 n_head_kv: int, head_dim: int, device, dtype):
+                 n_head_kv: int, head_dim: int, device, dtype,
+                 kv_format: Optional[str] = None):
+        if kv_format is not None and kv_format not in KV_CACHE_FORMATS:
+            raise ValueError(f"kv_format must be None or one of "
+                             f"{KV_CACHE_FORMATS}, got {kv_format!r}")
         self.max_len = max_len
         self.pos = 0
+        self.kv_format = kv_format
+        self.k_scale = self.v_scale = None
+        if kv_format is not None:
+            dtype = torch.float8_e4m3fn
+            self.k_scale, self.v_scale = (
+                [torch.ones(batch_size, max_len, n_head_kv, device=device)
+                 for _ in range(n_layer)] for _ in range(2))
         self.k = [torch.zeros(batch_size, max_len, n_head_kv, head_dim,
                               device=device, dtype=dtype)
                   for _ in range(n_layer)]
@@ -634,6 +701,13 @@ class KVCache:
                                    device=device)
         self.lens_dev = torch.zeros(batch_size, dtype=torch.int32,
                                     device=device)
+
+    def scales(self, i: int) -> dict:
+        """The `scales=` keyword of layer i's forward_cached: empty for a
+        bf16 cache."""
+        if self.kv_format is None:
+            return {}
+        return {"scales": (self.k_scale[i], self.v_scale[i])}
 
     def reset(self):
         self.pos = 0

@@ -7,7 +7,11 @@ torch SDPA/LayerNorm/CE/AdamW) with hand-written gfx950 HIP kernels:
 - K1  flash_attention   : MFMA/LDS-tiled causal attention fwd+bwd, GQA-aware,
                           optional per-document mask for packed sequences;
                           split-KV single-token decode over a KV cache with
-                          a fused RoPE + cache append
+                          a fused RoPE + cache append; the same over an
+                          e4m3 KV cache with per-(token, kv head) power-of-two
+                          scales (quantize_kv_fp8, kv_quantize_store, and
+                          k_scale / v_scale on the two decode ops): D + 4
+                          bytes per cached row instead of 2 D
 - K3  skinny_linear     : M <= 8 decode GEMM streaming bf16 or weight-only
                           e4m3 weights straight to registers
 - K3  skinny_linear_mfma: the same for M <= 32 on the matrix cores (MFMA),
@@ -41,6 +45,9 @@ from modalities_amd.ops.attention import (  # noqa: F401
     decode_attention,
     decode_attention_enabled,
     decode_rope_append,
+    dequantize_kv_fp8,
+    kv_quantize_store,
+    quantize_kv_fp8,
     set_decode_attention,
 )
 from modalities_amd.ops.adamw import fused_adamw_step  # noqa: F401

@@ -33,7 +33,16 @@ per-row lengths in a device tensor; `decode_rope_append` rotates the new
 token's q and k at a device-side position and appends k and v to the cache
 in one launch. Neither takes a host-side position, so a decode step can be
 captured once into a hipGraph and replayed per token. `set_decode_attention`
-/ MA_DECODE_ATTN=0 switch the model back to the prefill kernel for A/B."""
+/ MA_DECODE_ATTN=0 switch the model back to the prefill kernel for A/B.
+
+FP8 KV cache (csrc/attention_decode_fp8.hip): a cache may hold e4m3 codes
+[B, Lmax, Hkv, D] with one power-of-two fp32 scale per (row, position, kv
+head) [B, Lmax, Hkv] -- D + 4 bytes per row instead of 2 D. `quantize_kv_fp8`
+/ `dequantize_kv_fp8` define the format, `kv_quantize_store` is the prefill
+store, and `decode_rope_append` / `decode_attention` take the scales as
+k_scale / v_scale next to the code caches. scale * code is exact in bf16, so
+a bf16 cache of de-quantised values is an exact reference for the FP8 route
+(up to summation order); the CPU route is that expression in torch."""
 
 import math
 import os
@@ -434,6 +443,132 @@ def _check_index_arg(name, t, ref, B):
         raise ValueError(f"{name} must be contiguous")
 
 
+E4M3_MAX = 448.0
+KV_CACHE_FORMATS = ("fp8_e4m3",)
+
+
+def _check_cache_scales(k_cache, v_cache, k_scale, v_scale):
+    """bf16 caches take no scales; e4m3 caches need fp32 [B, Lmax, Hkv]
+    scales on their device. Returns True for an FP8 cache."""
+    if (k_scale is None) != (v_scale is None):
+        raise ValueError("give both k_scale and v_scale or neither")
+    fp8 = k_cache.dtype == torch.float8_e4m3fn
+    if k_cache.dtype != v_cache.dtype:
+        raise TypeError(f"k_cache is {k_cache.dtype}, v_cache "
+                        f"{v_cache.dtype}")
+    if k_scale is None:
+        if fp8:
+            raise ValueError("a float8_e4m3fn cache needs k_scale and "
+                             "v_scale")
+        return False
+    if not fp8:
+        raise TypeError(f"k_scale / v_scale go with float8_e4m3fn caches, "
+                        f"got {k_cache.dtype}")
+    for name, c, sc in (("k_scale", k_cache, k_scale),
+                        ("v_scale", v_cache, v_scale)):
+        if not isinstance(sc, torch.Tensor) or sc.dtype != torch.float32:
+            raise TypeError(f"{name} must be an fp32 tensor")
+        if tuple(sc.shape) != tuple(c.shape[:3]):
+            raise ValueError(f"{name} must be [B, Lmax, Hkv] = "
+                             f"{tuple(c.shape[:3])}, got {tuple(sc.shape)}")
+        if sc.device != c.device:
+            raise ValueError(f"{name} is on {sc.device}, its cache on "
+                             f"{c.device}")
+    return True
+
+
+def _quantize_kv_ref(x):
+    """The format in plain torch (CPU route and numerics reference)."""
+    xf = x.float()
+    amax = xf.abs().amax(dim=-1)
+    # amax / 448 = m * 2^e with m in [0.5, 1): ceil(log2) is e, or e - 1
+    # when the ratio is itself a power of two. Exact, no log.
+    m, e = torch.frexp(amax / E4M3_MAX)
+    e = torch.where(m == 0.5, e - 1, e)
+    scale = torch.where(amax > 0, torch.ldexp(torch.ones_like(amax), e),
+                        torch.ones_like(amax))
+    codes = (xf / scale.unsqueeze(-1)).to(torch.float8_e4m3fn)
+    return codes, scale
+
+
+def _kv_kernel_ok(*tensors):
+    return use_hip(*tensors) and tensors[0].shape[-1] in DECODE_HEAD_DIMS
+
+
+def quantize_kv_fp8(x: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """x [..., H, D] bf16 -> (codes float8_e4m3fn [..., H, D], scale fp32
+    [..., H]). Per vector x[D]: amax = max |x|, scale = 2^ceil(log2(amax /
+    448)) (1 for a zero vector), codes = e4m3(x / scale), round to nearest
+    even: the largest element lands in (224, 448], nothing saturates, and
+    scale * code is exact in bf16. Non-finite input is not checked (NaN in,
+    NaN codes out). x may be a strided view with unit stride in D."""
+    if not isinstance(x, torch.Tensor) or x.dtype != torch.bfloat16:
+        raise TypeError("quantize_kv_fp8: x must be a bf16 tensor")
+    if x.dim() < 2:
+        raise ValueError("quantize_kv_fp8: x must be [..., H, D]")
+    if not _kv_kernel_ok(x) or x.numel() == 0:
+        return _quantize_kv_ref(x)
+    x4 = x if x.dim() == 4 else x.reshape((-1, 1) + tuple(x.shape[-2:]))
+    if x4.stride(3) != 1 or any(st % 8 for st in x4.stride()[:3]) \
+            or x4.data_ptr() % 16:
+        x4 = x4.contiguous()
+    codes = torch.empty(x4.shape, dtype=torch.float8_e4m3fn, device=x.device)
+    scale = torch.empty(x4.shape[:3], dtype=torch.float32, device=x.device)
+    hip_ext().kv_quantize_store(x4, None, codes, scale, None, None, 0)
+    return codes.view(x.shape), scale.view(x.shape[:-1])
+
+
+def dequantize_kv_fp8(codes: torch.Tensor,
+                      scale: torch.Tensor) -> torch.Tensor:
+    """codes float8_e4m3fn [..., H, D], scale fp32 [..., H] -> bf16, exactly
+    scale * code (plain torch; the decode kernels never de-quantise to
+    memory)."""
+    if codes.dtype != torch.float8_e4m3fn or scale.dtype != torch.float32:
+        raise TypeError("dequantize_kv_fp8: codes must be float8_e4m3fn and "
+                        "scale fp32")
+    if tuple(scale.shape) != tuple(codes.shape[:-1]):
+        raise ValueError(f"dequantize_kv_fp8: scale {tuple(scale.shape)} does "
+                         f"not match codes {tuple(codes.shape)}")
+    return (codes.float() * scale.unsqueeze(-1)).to(torch.bfloat16)
+
+
+def kv_quantize_store(k: torch.Tensor, v: torch.Tensor,
+                      k_cache: torch.Tensor, v_cache: torch.Tensor,
+                      k_scale: torch.Tensor, v_scale: torch.Tensor,
+                      pos: int) -> None:
+    """The prefill store of an FP8 cache: quantise k, v [B, T, Hkv, D] bf16
+    (strided views are fine; k already rotated) as `quantize_kv_fp8` does
+    and write codes and scales to cache rows pos .. pos + T - 1. `pos` is a
+    host integer: prefill is not graph-captured."""
+    if k.dim() != 4 or k.shape != v.shape:
+        raise ValueError(f"k, v must be [B, T, Hkv, D] of one shape, got "
+                         f"{tuple(k.shape)} and {tuple(v.shape)}")
+    if k.dtype != torch.bfloat16 or v.dtype != torch.bfloat16:
+        raise TypeError("k, v must be bf16")
+    B, T, H, D = k.shape
+    if k_cache.dim() != 4 or k_cache.shape != v_cache.shape \
+            or (k_cache.shape[0], k_cache.shape[2], k_cache.shape[3]) \
+            != (B, H, D):
+        raise ValueError(f"caches {tuple(k_cache.shape)} / "
+                         f"{tuple(v_cache.shape)} do not match k "
+                         f"{tuple(k.shape)}")
+    if not _check_cache_scales(k_cache, v_cache, k_scale, v_scale):
+        raise ValueError("kv_quantize_store needs k_scale and v_scale")
+    if not 0 <= pos <= k_cache.shape[1] - T:
+        raise ValueError(f"rows {pos} .. {pos + T} do not fit a cache of "
+                         f"{k_cache.shape[1]}")
+    if _kv_kernel_ok(k, v, k_cache, v_cache, k_scale, v_scale):
+        if any(st % 8 for st in k.stride()[:3] + v.stride()[:3]):
+            k, v = k.contiguous(), v.contiguous()
+        hip_ext().kv_quantize_store(k, v, k_cache, k_scale, v_cache, v_scale,
+                                    pos)
+        return
+    for x, c, sc in ((k, k_cache, k_scale), (v, v_cache, v_scale)):
+        codes, scale = _quantize_kv_ref(x)
+        c[:, pos:pos + T] = codes
+        sc[:, pos:pos + T] = scale
+
+
 def _check_decode_args(q, k_cache, v_cache, kv_lens):
     if q.dim() != 4 or q.shape[1] != 1:
         raise ValueError(f"q must be [B, 1, Hq, D], got {tuple(q.shape)}")
@@ -468,16 +603,39 @@ def _decode_attention_ref(q, k_cache, v_cache, kv_lens):
     return o
 
 
+def _dequantize_prefix(codes, scale, kv_lens):
+    """De-quantised copy of an FP8 cache for the torch route; rows at or
+    beyond a length stay zero (they are never read, and may hold NaN)."""
+    out = torch.zeros(codes.shape, dtype=torch.bfloat16, device=codes.device)
+    for b, n in enumerate(kv_lens.tolist()):
+        n = min(max(n, 0), codes.shape[1])
+        out[b, :n] = dequantize_kv_fp8(codes[b, :n], scale[b, :n])
+    return out
+
+
 def decode_attention(q: torch.Tensor, k_cache: torch.Tensor,
-                     v_cache: torch.Tensor,
-                     kv_lens: torch.Tensor) -> torch.Tensor:
+                     v_cache: torch.Tensor, kv_lens: torch.Tensor,
+                     k_scale: Optional[torch.Tensor] = None,
+                     v_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Single-token attention over a KV cache. q: [B,1,Hq,D] (rows may be
     strided); k_cache, v_cache: [B,Lmax,Hkv,D], read in place through their
     strides; kv_lens: contiguous int32 [B] on q's device. Row b attends to
     cache rows 0 .. kv_lens[b]-1 (clamped to [0, Lmax]; 0 gives zeros) and
     nothing at or beyond the length is read. Returns o [B,1,Hq,D].
-    D in {64, 80, 128}; inference only (no autograd)."""
+    D in {64, 80, 128}; inference only (no autograd).
+
+    FP8 cache: k_cache, v_cache hold float8_e4m3fn codes and k_scale,
+    v_scale their fp32 [B,Lmax,Hkv] scales (`quantize_kv_fp8`); the result
+    is attention over scale * code."""
     _check_decode_args(q, k_cache, v_cache, kv_lens)
+    if _check_cache_scales(k_cache, v_cache, k_scale, v_scale):
+        if use_hip(q, k_cache, v_cache, kv_lens, k_scale, v_scale):
+            o, _ = hip_ext().decode_attn_fp8_fwd(q, k_cache, k_scale, v_cache,
+                                                 v_scale, kv_lens)
+            return o
+        return _decode_attention_ref(
+            q, _dequantize_prefix(k_cache, k_scale, kv_lens),
+            _dequantize_prefix(v_cache, v_scale, kv_lens), kv_lens)
     if use_hip(q, k_cache, v_cache, kv_lens):
         o, _ = hip_ext().decode_attn_fwd(q, k_cache, v_cache, kv_lens)
         return o
@@ -510,15 +668,22 @@ def _decode_rope_append_ref(q, k, v, cos, sin, pos, k_cache, v_cache):
 def decode_rope_append(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
                        cos: Optional[torch.Tensor],
                        sin: Optional[torch.Tensor], pos: torch.Tensor,
-                       k_cache: torch.Tensor,
-                       v_cache: torch.Tensor) -> torch.Tensor:
+                       k_cache: torch.Tensor, v_cache: torch.Tensor,
+                       k_scale: Optional[torch.Tensor] = None,
+                       v_scale: Optional[torch.Tensor] = None
+                       ) -> torch.Tensor:
     """One decode step's RoPE and cache append. q: [B,1,Hq,D]; k, v:
     [B,1,Hkv,D] (rows may be strided views, e.g. into the fused-QKV
     projection output); cos/sin: fp32 [>=Lmax, D/2] tables or None (no
     rotation); pos: contiguous int32 [B] on q's device. Rotates q and k at
     table row pos[b], stores the rotated k and v to cache[b, pos[b]] and
     returns the rotated q (contiguous). A row with pos[b] outside [0, Lmax)
-    leaves the cache untouched and returns zeros for q."""
+    leaves the cache untouched and returns zeros for q.
+
+    FP8 cache: with float8_e4m3fn caches and their fp32 [B,Lmax,Hkv]
+    k_scale / v_scale, the rotated k (rounded to bf16 first, the value a
+    bf16 cache would hold) and v are stored as `quantize_kv_fp8` gives
+    them, codes and scales, in the same single launch."""
     if q.dim() != 4 or q.shape[1] != 1 or k.shape != v.shape \
             or k.dim() != 4 or k.shape[:2] != q.shape[:2] \
             or k.shape[3] != q.shape[3]:
@@ -540,7 +705,38 @@ def decode_rope_append(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
         raise ValueError("cos/sin must be [>=Lmax, D/2], got "
                          f"{tuple(cos.shape)} for Lmax={k_cache.shape[1]}")
     _check_index_arg("pos", pos, q, B)
+    if _check_cache_scales(k_cache, v_cache, k_scale, v_scale):
+        if _kv_kernel_ok(q, k, v, k_cache, v_cache, pos, k_scale, v_scale):
+            return hip_ext().decode_rope_append_fp8(
+                q, k, v, cos, sin, pos, k_cache, k_scale, v_cache, v_scale)
+        return _decode_rope_append_fp8_ref(q, k, v, cos, sin, pos, k_cache,
+                                           v_cache, k_scale, v_scale)
     if use_hip(q, k, v, k_cache, v_cache, pos):
         return hip_ext().decode_rope_append(q, k, v, cos, sin, pos, k_cache,
                                             v_cache)
     return _decode_rope_append_ref(q, k, v, cos, sin, pos, k_cache, v_cache)
+
+
+def _decode_rope_append_fp8_ref(q, k, v, cos, sin, pos, k_cache, v_cache,
+                                k_scale, v_scale):
+    """The bf16 step on a one-row scratch cache per batch row, quantised
+    into the FP8 cache at pos[b]."""
+    Lmax = k_cache.shape[1]
+    kb = torch.zeros(k.shape, dtype=k.dtype, device=k.device)
+    vb = torch.zeros_like(kb)
+    q_out = torch.zeros(q.shape, dtype=q.dtype, device=q.device)
+    zero = torch.zeros(1, dtype=torch.int32, device=q.device)
+    for b, p in enumerate(pos.tolist()):
+        if not 0 <= p < Lmax:
+            continue
+        # table row p, scratch cache row 0
+        c = None if cos is None else cos[p:p + 1]
+        s = None if sin is None else sin[p:p + 1]
+        q_out[b:b + 1] = _decode_rope_append_ref(
+            q[b:b + 1], k[b:b + 1], v[b:b + 1], c, s, zero, kb[b:b + 1],
+            vb[b:b + 1])
+        for x, cache, sc in ((kb, k_cache, k_scale), (vb, v_cache, v_scale)):
+            codes, scale = _quantize_kv_ref(x[b, 0])
+            cache[b, p] = codes
+            sc[b, p] = scale
+    return q_out

@@ -8,6 +8,7 @@ carry it to GPU boxes. Usage: python -m modalities_amd.ops.build
 import subprocess
 import sys
 import sysconfig
+import tempfile
 from pathlib import Path
 
 import torch
@@ -32,6 +33,17 @@ SOURCES = [
     "bindings.cpp",
 ]
 
+# Compiled on their own, with packed fp32 arithmetic (v_pk_fma_f32 and kin)
+# switched off, and linked into the same library; SOURCES keep the flags
+# they were tuned and validated with.
+NO_PACKED_FP32_SOURCES = [
+    "attention_decode_fp8.hip",
+]
+NO_PACKED_FP32_FLAGS = ["-Xclang", "-target-feature", "-Xclang",
+                        "-packed-fp32-ops"]
+
+HEADERS = ["common.h", "attn_common.h", "attention_decode_common.h"]
+
 
 def build_extension(verbose: bool = True, arch: str = "gfx950") -> Path:
     torch_lib = Path(torch.__file__).parent / "lib"
@@ -39,26 +51,37 @@ def build_extension(verbose: bool = True, arch: str = "gfx950") -> Path:
     abi = int(torch._C._GLIBCXX_USE_CXX11_ABI)
 
     srcs = [str(CSRC / s) for s in SOURCES]
-    newest_src = max((CSRC / s).stat().st_mtime for s in SOURCES)
-    newest_src = max(newest_src, (CSRC / "common.h").stat().st_mtime)
+    newest_src = max((CSRC / s).stat().st_mtime
+                     for s in SOURCES + NO_PACKED_FP32_SOURCES + HEADERS)
     if OUT.exists() and OUT.stat().st_mtime > newest_src:
         if verbose:
             print(f"[build] {OUT} up to date")
         return OUT
 
-    cmd = (
+    common = (
         ["hipcc", f"--offload-arch={arch}", "-O3", "-std=c++17", "-fPIC",
-         "-shared", "-DTORCH_EXTENSION_NAME=_hip_ops",
+         "-DTORCH_EXTENSION_NAME=_hip_ops",
          f"-D_GLIBCXX_USE_CXX11_ABI={abi}",
          "-DUSE_ROCM=1", "-D__HIP_PLATFORM_AMD__=1",
-         "-Wno-unused-result", "-fno-gpu-rdc",
-         "-x", "hip"]
+         "-Wno-unused-result", "-fno-gpu-rdc"]
         + [f"-I{p}" for p in includes]
-        + srcs
-        + [f"-L{torch_lib}", "-ltorch", "-ltorch_cpu", "-ltorch_hip", "-lc10",
-           "-lc10_hip", "-ltorch_python", "-lamdhip64",
-           f"-Wl,-rpath,{torch_lib}", "-o", str(OUT)]
     )
+    with tempfile.TemporaryDirectory(prefix="hip_ops_") as tmp:
+        objs = []
+        for s in NO_PACKED_FP32_SOURCES:
+            objs.append(str(Path(tmp) / (Path(s).stem + ".o")))
+            _run(common + NO_PACKED_FP32_FLAGS
+                 + ["-c", "-x", "hip", str(CSRC / s), "-o", objs[-1]],
+                 verbose)
+        # the objects go last: "-x none" ends the language override
+        _run(common + ["-shared", "-x", "hip"] + srcs + ["-x", "none"] + objs
+             + [f"-L{torch_lib}", "-ltorch", "-ltorch_cpu", "-ltorch_hip",
+                "-lc10", "-lc10_hip", "-ltorch_python", "-lamdhip64",
+                f"-Wl,-rpath,{torch_lib}", "-o", str(OUT)], verbose)
+    return OUT
+
+
+def _run(cmd, verbose: bool) -> None:
     if verbose:
         print("[build]", " ".join(cmd))
     result = subprocess.run(cmd, capture_output=True, text=True)
@@ -68,7 +91,6 @@ def build_extension(verbose: bool = True, arch: str = "gfx950") -> Path:
         raise RuntimeError(f"hipcc failed with code {result.returncode}")
     if verbose and result.stderr:
         print(result.stderr[-2000:])
-    return OUT
 
 
 if __name__ == "__main__":

@@ -122,6 +122,25 @@ torch::Tensor decode_rope_append(torch::Tensor q, torch::Tensor k,
                                  c10::optional<torch::Tensor> sin_t,
                                  torch::Tensor pos, torch::Tensor k_cache,
                                  torch::Tensor v_cache);
+void kv_quantize_store(torch::Tensor k, c10::optional<torch::Tensor> v,
+                       torch::Tensor k_codes, torch::Tensor k_scale,
+                       c10::optional<torch::Tensor> v_codes,
+                       c10::optional<torch::Tensor> v_scale, long pos);
+torch::Tensor decode_rope_append_fp8(torch::Tensor q, torch::Tensor k,
+                                     torch::Tensor v,
+                                     c10::optional<torch::Tensor> cos_t,
+                                     c10::optional<torch::Tensor> sin_t,
+                                     torch::Tensor pos, torch::Tensor k_codes,
+                                     torch::Tensor k_scale,
+                                     torch::Tensor v_codes,
+                                     torch::Tensor v_scale);
+std::vector<torch::Tensor> decode_attn_fp8_fwd(torch::Tensor q,
+                                               torch::Tensor k_codes,
+                                               torch::Tensor k_scale,
+                                               torch::Tensor v_codes,
+                                               torch::Tensor v_scale,
+                                               torch::Tensor kv_lens,
+                                               long kv_chunk);
 torch::Tensor skinny_linear(torch::Tensor x, torch::Tensor w,
                             c10::optional<torch::Tensor> scale,
                             c10::optional<torch::Tensor> bias);
@@ -301,6 +320,24 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("q"), py::arg("k"), py::arg("v"), py::arg("cos"),
         py::arg("sin"), py::arg("pos"), py::arg("k_cache"),
         py::arg("v_cache"));
+  // The same three steps over an e4m3 KV cache (codes + per-row scales).
+  m.def("kv_quantize_store", &kv_quantize_store,
+        "quantise k (and v) bf16 [B,T,Hkv,D] per (row, head) to e4m3 codes "
+        "and power-of-two fp32 scales, written to cache rows pos .. pos+T-1",
+        py::arg("k"), py::arg("v"), py::arg("k_codes"), py::arg("k_scale"),
+        py::arg("v_codes"), py::arg("v_scale"), py::arg("pos"));
+  m.def("decode_rope_append_fp8", &decode_rope_append_fp8,
+        "decode_rope_append into an e4m3 cache: the rotated k (rounded to "
+        "bf16) and v are quantised into codes and scales at row pos[b]",
+        py::arg("q"), py::arg("k"), py::arg("v"), py::arg("cos"),
+        py::arg("sin"), py::arg("pos"), py::arg("k_codes"),
+        py::arg("k_scale"), py::arg("v_codes"), py::arg("v_scale"));
+  m.def("decode_attn_fp8_fwd", &decode_attn_fp8_fwd,
+        "decode_attn_fwd over e4m3 code caches [B,Lmax,Hkv,D] with fp32 "
+        "scales [B,Lmax,Hkv]; returns (o, lse [B,Hq,1])",
+        py::arg("q"), py::arg("k_codes"), py::arg("k_scale"),
+        py::arg("v_codes"), py::arg("v_scale"), py::arg("kv_lens"),
+        py::arg("kv_chunk") = 0);
   // Skinny GEMM for single-token decoding (weight-only e4m3 or bf16).
   m.def("skinny_linear", &skinny_linear,
         "y [M,N] bf16 = x [M,K] bf16 . w [N,K]^T for 1 <= M <= 8, K % 16 == 0; "

@@ -5,12 +5,17 @@
          (.contiguous() of cache[:, :n]; a no-op view at batch 1) and sent
          through attn_fwd with Tq = 1, q_offset = n - 1
 
+  fp8    (--kv-format fp8_e4m3) decode_attn_fp8_fwd over the same cache as
+         e4m3 codes + per-(token, kv head) fp32 scales, against `split` from
+         the same run; its bytes are 2 * B * n * Hkv * (D + 4)
+
 at the same shapes. Times come from device events around `--iters` calls
 after a warm-up; the K/V rate is the bytes the algorithm needs
 (2 * B * n * Hkv * D * 2) over that time.
 
     PYTHONPATH=. python tools/decode_attn_bench.py [--ctx 512 2048 3968]
         [--batch 1 8] [--shape 32:32:80 32:8:128] [--kv-chunk 0 128 512]
+        [--kv-format fp8_e4m3] [--no-flash]
 """
 
 import argparse
@@ -42,6 +47,10 @@ def main():
     ap.add_argument("--kv-chunk", type=int, nargs="+", default=[0],
                     help="0 = the compiled default")
     ap.add_argument("--lmax", type=int, default=4096)
+    ap.add_argument("--kv-format", choices=["bf16", "fp8_e4m3"],
+                    default="bf16")
+    ap.add_argument("--no-flash", action="store_true",
+                    help="skip the prefill-kernel baseline")
     ap.add_argument("--iters", type=int, default=200)
     args = ap.parse_args()
     print(f"default kv_chunk {ext.decode_attn_kv_chunk()}")
@@ -51,6 +60,9 @@ def main():
             q = torch.randn(B, 1, Hq, D, device="cuda").bfloat16()
             kc = torch.randn(B, args.lmax, Hkv, D, device="cuda").bfloat16()
             vc = torch.randn(B, args.lmax, Hkv, D, device="cuda").bfloat16()
+            if args.kv_format == "fp8_e4m3":
+                from modalities_amd.ops import quantize_kv_fp8
+                (kq, ks), (vq, vs) = quantize_kv_fp8(kc), quantize_kv_fp8(vc)
             for n in args.ctx:
                 lens = torch.full((B,), n, dtype=torch.int32, device="cuda")
                 kv_bytes = 2 * B * n * Hkv * D * 2
@@ -59,10 +71,15 @@ def main():
                     return ext.attn_fwd(q, kc[:, :n].contiguous(),
                                         vc[:, :n].contiguous(), True, n - 1)
 
-                us_f = timed(flash, args.iters)
-                line = (f"Hq{Hq} Hkv{Hkv} D{D} B{B} ctx{n}: flash "
-                        f"{us_f:7.1f} us {kv_bytes / us_f / 1e6:7.3f} TB/s |")
-                o_f = flash()[0]
+                line = f"Hq{Hq} Hkv{Hkv} D{D} B{B} ctx{n}:"
+                if args.no_flash:
+                    us_f = float("nan")
+                    o_f = ext.decode_attn_fwd(q, kc, vc, lens, 0)[0]
+                else:
+                    us_f = timed(flash, args.iters)
+                    line += (f" flash {us_f:7.1f} us "
+                             f"{kv_bytes / us_f / 1e6:7.3f} TB/s |")
+                    o_f = flash()[0]
                 for ch in args.kv_chunk:
                     us_s = timed(lambda: ext.decode_attn_fwd(q, kc, vc, lens,
                                                              ch), args.iters)
@@ -71,6 +88,16 @@ def main():
                     line += (f" split[{ch}] {us_s:6.1f} us "
                              f"{kv_bytes / us_s / 1e6:6.3f} TB/s "
                              f"({us_f / us_s:4.1f}x, maxdiff {err:.1e}) |")
+                    if args.kv_format == "fp8_e4m3":
+                        fp8 = lambda: ext.decode_attn_fp8_fwd(
+                            q, kq, ks, vq, vs, lens, ch)
+                        us_8 = timed(fp8, args.iters)
+                        b8 = 2 * B * n * Hkv * (D + 4)
+                        err = (fp8()[0].float() - o_s.float()).abs().max()
+                        line += (f" fp8[{ch}] {us_8:6.1f} us "
+                                 f"{b8 / us_8 / 1e6:6.3f} TB/s "
+                                 f"({us_8 / us_s:4.2f}x the split time, "
+                                 f"maxdiff {err.item():.1e}) |")
                 print(line, flush=True)
 
 

@@ -3,7 +3,8 @@ re-forward on the flagship 2.7B shape (GPU).
 
     PYTHONPATH=. python tools/decode_bench.py [--ctx 512 2048 3968]
         [--batch 1 [16 32 ...]] [--impl {flash,split,graph}]
-        [--weights {off,bf16,fp8_e4m3}]
+        [--weights {off,bf16,fp8_e4m3}] [--kv-format {bf16,fp8_e4m3}]
+        [--kv-logit-diff]
 
 --impl picks the route of the cached single-token step: `flash` is the
 prefill kernel on the copied cache prefix (set_decode_attention(False)),
@@ -17,6 +18,10 @@ prepare them (GPT2LLM.prepare_decode_weights) for the in-tree skinny GEMMs
 (the VALU kernel up to batch 8, the MFMA kernel for batch 9..32), on the bf16
 weights or on weight-only FP8. --batch takes one or more batch sizes; each
 runs every --ctx.
+
+--kv-format fp8_e4m3 decodes on an e4m3 KV cache (new_kv_cache(kv_format=));
+--kv-logit-diff prints the largest |logit difference| of 64 greedy steps on
+that cache against the same tokens on a bf16 cache.
 """
 
 import argparse
@@ -40,14 +45,15 @@ def build_model():
     return m.to(torch.bfloat16).eval(), cfg
 
 
-def time_cached(model, ids, iters, impl):
+def time_cached(model, ids, iters, impl, kv_format=None):
     """ms per generated token of the cached decode loop."""
     from modalities_amd.inference.text_generation import DecodeGraph
     from modalities_amd.ops import set_decode_attention
     set_decode_attention(impl != "flash")
     B, ctx = ids.shape
     try:
-        cache = model.new_kv_cache(B, max_len=ctx + 2 * iters + 8)
+        cache = model.new_kv_cache(B, max_len=ctx + 2 * iters + 8,
+                                   kv_format=kv_format)
         out = model.forward_cached({"input_ids": ids}, cache)["logits"]
         graph = None
         if impl == "graph":
@@ -92,6 +98,26 @@ def logit_error(model, ids):
     return rel, (got - ref).abs().max().item(), ref.abs().max().item(), same
 
 
+def kv_logit_diff(model, ids, steps=64):
+    """Largest |logit difference| over `steps` greedy tokens (chosen on the
+    bf16 cache) between an FP8 and a bf16 KV cache, and the share of steps
+    with the same argmax."""
+    B, ctx = ids.shape
+    caches = [model.new_kv_cache(B, max_len=ctx + steps + 8, kv_format=f)
+              for f in (None, "fp8_e4m3")]
+    outs = [model.forward_cached({"input_ids": ids}, c)["logits"][:, -1:]
+            for c in caches]
+    worst, top, same = 0.0, 0.0, 0
+    for _ in range(steps):
+        nxt = outs[0].argmax(-1)
+        outs = [model.forward_cached({"input_ids": nxt}, c)["logits"].float()
+                for c in caches]
+        worst = max(worst, (outs[0] - outs[1]).abs().max().item())
+        top = max(top, outs[0].abs().max().item())
+        same += (outs[0].argmax(-1) == outs[1].argmax(-1)).float().mean().item()
+    return worst, top, same / steps
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--ctx", type=int, nargs="+", default=[512, 2048, 3968])
@@ -104,12 +130,18 @@ def main():
     ap.add_argument("--logit-error", action="store_true",
                     help="with --weights bf16/fp8_e4m3: also print the "
                          "error of a step's logits against the bf16 route")
+    ap.add_argument("--kv-format", choices=["bf16", "fp8_e4m3"],
+                    default="bf16")
+    ap.add_argument("--kv-logit-diff", action="store_true",
+                    help="print the logit difference of an FP8 against a "
+                         "bf16 KV cache over 64 greedy tokens")
     ap.add_argument("--no-reforward", action="store_true",
                     help="skip the full-context re-forward comparison")
     args = ap.parse_args()
     model, cfg = build_model()
     if args.weights != "off":
         model.prepare_decode_weights(args.weights)
+    kv_format = None if args.kv_format == "bf16" else args.kv_format
     for batch in args.batch:
         for ctx in args.ctx:
             ids = torch.randint(0, cfg.vocab_size, (batch, ctx),
@@ -120,11 +152,17 @@ def main():
                     print(f"ctx {ctx}: logits {args.weights} vs bf16 route: "
                           f"rel l2 {rel:.3e}, max abs {mx:.3e} (max |logit| "
                           f"{top:.3f}), same argmax {same:.2f}")
-                cached_ms = time_cached(model, ids, args.iters, args.impl)
+                if args.kv_logit_diff:
+                    worst, top, same = kv_logit_diff(model, ids)
+                    print(f"ctx {ctx}: logits fp8_e4m3 vs bf16 KV cache, 64 "
+                          f"greedy tokens: max abs diff {worst:.3e} (max "
+                          f"|logit| {top:.3f}), same argmax {same:.3f}")
+                cached_ms = time_cached(model, ids, args.iters, args.impl,
+                                        kv_format)
                 if args.no_reforward:
                     print(f"ctx {ctx}: cached {cached_ms:.2f} ms/tok  "
                           f"[batch {batch}, {args.impl}, "
-                          f"weights {args.weights}]")
+                          f"weights {args.weights}, kv {args.kv_format}]")
                     continue
 
                 full = ids
