@@ -180,6 +180,7 @@ def _build_text_inference_component(config_path: Path):
         sample_key=settings.referencing_keys.get("sample_key", "input_ids"),
         prediction_key=settings.referencing_keys.get("prediction_key", "logits"),
         use_decode_graph=gen_cfg.get("use_decode_graph", True),
+        device_sampling=gen_cfg.get("device_sampling", False),
         decode_weight_format=gen_cfg.get("decode_weight_format"),
         kv_cache_format=gen_cfg.get("kv_cache_format"))
     return comp

@@ -23,7 +23,14 @@ to batch 8, the MFMA kernel for batch 9..32), on weight-only FP8 for
 has the model allocate an e4m3 KV cache (GPT2LLM.new_kv_cache(kv_format=...)):
 0.5x + 4 bytes per cached row, read by the FP8 decode kernels; the prefill
 stores quantised. It pays where the cache, not the weights, is the traffic:
-large batch times long context (profiles/decode_attention.md)."""
+large batch times long context (profiles/decode_attention.md).
+
+`device_sampling=True` (default off) samples with `ops.sample_logits`: one
+HIP kernel for temperature, top-k, top-p and the draw, reading the logits
+where lm_head left them. A captured decode step then ends in `torch.rand`
+and that kernel, which writes the next id into the graph's own input
+buffer: between two replays the host only reads the id back for the eod
+check (profiles/sampling.md)."""
 
 import sys
 from typing import Optional
@@ -41,11 +48,19 @@ class DecodeGraph:
     [B, 1, V] (valid after `step`). Single stream; one warm-up step runs on
     a side stream first and is then undone (the cache row it wrote is the
     one the first replay rewrites). The host mirror cache.pos is advanced
-    per replay; the device counters advance inside the graph."""
+    per replay; the device counters advance inside the graph.
 
-    def __init__(self, model, cache, sample_key: str, prediction_key: str):
+    With `sampler` = (temperature, top_k, top_p) the captured step goes on
+    to draw `u` = torch.rand(B) (fresh numbers per replay: the capture
+    registers the default generator) and to sample the next id from
+    `logits` into `ids` with ops.sample_logits. After a replay `ids` is the
+    next step's input already and `step()` takes no argument."""
+
+    def __init__(self, model, cache, sample_key: str, prediction_key: str,
+                 sampler: Optional[tuple] = None):
         self.cache = cache
         self.sample_key = sample_key
+        self.sampler = sampler
         dev = cache.pos_dev.device
         B = cache.pos_dev.shape[0]
         self.ids = torch.zeros(B, 1, dtype=torch.long, device=dev)
@@ -57,33 +72,48 @@ class DecodeGraph:
             cache.pos = pos
             cache.pos_dev.fill_(pos)
 
+        def one_step():
+            logits = model.forward_cached({sample_key: self.ids},
+                                          cache)[prediction_key]
+            if sampler is not None:
+                from modalities_amd.ops import sample_logits
+                self.u = torch.rand(B, device=dev)
+                sample_logits(logits[:, -1], self.u, self.ids, *sampler)
+            return logits
+
         try:
             side = torch.cuda.Stream(device=dev)
             side.wait_stream(torch.cuda.current_stream(dev))
             with torch.cuda.stream(side):
-                model.forward_cached({sample_key: self.ids}, cache)
+                one_step()
             torch.cuda.current_stream(dev).wait_stream(side)
             rewind()
             self.graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self.graph):
-                self.logits = model.forward_cached(
-                    {sample_key: self.ids}, cache)[prediction_key]
+                self.logits = one_step()
         finally:
             rewind()
 
-    def step(self, next_ids: torch.Tensor) -> torch.Tensor:
-        """Decode one token per row; returns the static logits [B, 1, V]."""
+    def step(self, next_ids: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Decode one token per row; returns the static logits [B, 1, V].
+        `next_ids` None (a graph with a sampler, from its second step on)
+        decodes the ids the last replay sampled."""
         if self.cache.pos + 1 > self.cache.max_len:
             raise ValueError(f"KV cache overflow: {self.cache.pos}+1 > "
                              f"{self.cache.max_len}")
-        self.ids.copy_(next_ids)
+        if next_ids is not None:
+            self.ids.copy_(next_ids)
+        elif self.sampler is None:
+            raise ValueError("DecodeGraph.step: a graph without a sampler "
+                             "needs next_ids")
         self.graph.replay()
         self.cache.pos += 1
         return self.logits
 
 
 def capture_decode_graph(model, cache, sample_key: str = "input_ids",
-                         prediction_key: str = "logits"
+                         prediction_key: str = "logits",
+                         sampler: Optional[tuple] = None
                          ) -> Optional[DecodeGraph]:
     """A DecodeGraph when the model decodes on the GPU through the decode
     kernels and the capture succeeds; None (decode eagerly) otherwise."""
@@ -92,7 +122,9 @@ def capture_decode_graph(model, cache, sample_key: str = "input_ids",
             or not route(cache.pos_dev):
         return None
     try:
-        return DecodeGraph(model, cache, sample_key, prediction_key)
+        if sampler is None:
+            return DecodeGraph(model, cache, sample_key, prediction_key)
+        return DecodeGraph(model, cache, sample_key, prediction_key, sampler)
     except Exception as e:
         print(f"# hipGraph capture of the decode step unavailable "
               f"({type(e).__name__}: {e}); decoding eagerly",
@@ -108,7 +140,8 @@ class TextInferenceComponent:
                  top_k: Optional[int] = None, top_p: Optional[float] = None,
                  use_decode_graph: bool = True,
                  decode_weight_format: Optional[str] = None,
-                 kv_cache_format: Optional[str] = None):
+                 kv_cache_format: Optional[str] = None,
+                 device_sampling: bool = False):
         if decode_weight_format is not None \
                 and not hasattr(model, "prepare_decode_weights"):
             raise ValueError(
@@ -138,10 +171,23 @@ class TextInferenceComponent:
         self.use_decode_graph = use_decode_graph
         self.decode_weight_format = decode_weight_format
         self.kv_cache_format = kv_cache_format
+        self.device_sampling = device_sampling
+
+    def _sampler(self) -> tuple:
+        """(temperature, top_k, top_p) as ops.sample_logits takes them."""
+        return (float(self.temperature), int(self.top_k or 0),
+                float(self.top_p or 0.0))
 
     def _sample(self, logits: torch.Tensor) -> torch.Tensor:
         """Greedy (temperature==0) or temperature sampling with optional
-        top-k / nucleus (top-p) filtering."""
+        top-k / nucleus (top-p) filtering. With device_sampling: the same
+        through ops.sample_logits, on the logits as they are stored."""
+        if self.device_sampling:
+            from modalities_amd.ops import sample_logits
+            B = logits.shape[0]
+            u = torch.rand(B, device=logits.device)
+            ids = torch.empty(B, 1, dtype=torch.long, device=logits.device)
+            return sample_logits(logits, u, ids, *self._sampler())
         if self.temperature <= 0:
             return logits.argmax(dim=-1, keepdim=True)
         logits = logits / self.temperature
@@ -197,9 +243,12 @@ class TextInferenceComponent:
 
         graph = None
         graph_tried = not (self.use_decode_graph and cache is not None)
+        next_id = None   # set where a graph replay sampled it on the device
         for i in range(max_new):
-            logits = out[self.prediction_key][:, -1, :].float()
-            next_id = self._sample(logits)
+            if next_id is None:
+                logits = out[self.prediction_key][:, -1, :]
+                next_id = self._sample(logits if self.device_sampling
+                                       else logits.float())
             token = next_id.item()
             if eod_id is not None and token == eod_id:
                 break
@@ -216,7 +265,13 @@ class TextInferenceComponent:
                     graph_tried = True
                     graph = capture_decode_graph(
                         self.model, cache, self.sample_key,
-                        self.prediction_key)
+                        self.prediction_key,
+                        self._sampler() if self.device_sampling else None)
+                if graph is not None and graph.sampler is not None:
+                    out = {self.prediction_key: graph.step(
+                        None if next_id is graph.ids else next_id)}
+                    next_id = graph.ids
+                    continue
                 if graph is not None:
                     out = {self.prediction_key: graph.step(next_id)}
                 else:
@@ -225,6 +280,7 @@ class TextInferenceComponent:
             else:
                 input_ids = torch.cat([input_ids, next_id], dim=1)
                 out = self.model({self.sample_key: input_ids})
+            next_id = None
         if echo:
             sys.stdout.write("\n")
         return self.tokenizer.decode(generated)

@@ -16,6 +16,9 @@ torch SDPA/LayerNorm/CE/AdamW) with hand-written gfx950 HIP kernels:
                           e4m3 weights straight to registers
 - K3  skinny_linear_mfma: the same for M <= 32 on the matrix cores (MFMA),
                           e4m3 widened to bf16 in registers
+- K3  sample_logits     : temperature / top-k / top-p token sampler on the
+                          logits row, radix selects instead of a sort; one
+                          launch, capturable into the decode graph
 - K4  rope              : fused rotate-half RoPE on q,k
 - K5  rms_norm          : wave-level reduction norm fwd+bwd
 - K5  layer_norm        : register-resident row LayerNorm fwd+bwd (bf16)
@@ -57,3 +60,4 @@ from modalities_amd.ops.decode_linear import (  # noqa: F401
     skinny_linear,
     skinny_linear_mfma,
 )
+from modalities_amd.ops.sampling import sample_logits  # noqa: F401

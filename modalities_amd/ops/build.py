@@ -30,6 +30,7 @@ SOURCES = [
     "attention_decode.hip",
     "decode_gemv.hip",
     "decode_gemv_mfma.hip",
+    "sample_logits.hip",
     "bindings.cpp",
 ]
 

@@ -150,6 +150,10 @@ torch::Tensor skinny_linear_mfma(torch::Tensor x, torch::Tensor w,
                                  c10::optional<torch::Tensor> bias,
                                  long rt, long ksplit);
 long skinny_linear_mfma_max_m();
+void sample_logits(torch::Tensor logits, torch::Tensor u,
+                   torch::Tensor out_ids, double temperature, long top_k,
+                   double top_p);
+long sample_logits_row_in_lds(long V, long elem_size, long device);
 
 // v1/v2 dispatch: v2 (8-wave, 2 waves/SIMD) is the perf path; v1 kept for
 // A/B and as a fallback switch. Flip with set_attn_impl / MA_ATTN_IMPL.
@@ -355,4 +359,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("ksplit") = 0);
   m.def("skinny_linear_mfma_max_m", &skinny_linear_mfma_max_m,
         "largest batch (rows of x) skinny_linear_mfma takes");
+  m.def("sample_logits", &sample_logits,
+        "temperature / top-k / top-p sampling of one id per logits row "
+        "(bf16 or fp32 [B, V], row-strided) with u fp32 [B] in [0, 1), "
+        "written to out_ids int64 [B] or [B, 1]; temperature <= 0 is greedy");
+  m.def("sample_logits_row_in_lds", &sample_logits_row_in_lds,
+        "1 when sample_logits keeps a [., V] row of this element size in "
+        "LDS on the device, 0 when it re-reads global memory");
 }
