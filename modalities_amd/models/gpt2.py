@@ -22,6 +22,7 @@ from modalities_amd.exceptions import ConfigError
 from modalities_amd.ops.attention import (DECODE_HEAD_DIMS, KV_CACHE_FORMATS,
                                           _doc_visible, decode_attention,
                                           decode_attention_enabled,
+                                          decode_chunk_tokens,
                                           decode_rope_append,
                                           dequantize_kv_fp8, document_starts,
                                           fused_qkv_rope_attention,
@@ -242,7 +243,16 @@ class CausalSelfAttention(nn.Module):
         read: a prefill attends on its fresh bf16 K/V, a single token on the
         cache including its own quantised row, and a chunk at pos > 0
         de-quantises the whole prefix first -- a slow path, meant for
-        tests and the occasional chunked prefill, not for decoding."""
+        tests and the occasional chunked prefill, not for decoding.
+
+        A multi-token step with dec given (GPT2LLM.forward_cached gives it
+        for 2 <= T <= `decode_chunk_tokens()` at pos > 0; lens_dev then
+        holds pos + T) stores its K/V as above and attends through
+        `decode_attention`, which reads the cache in place: no copy of the
+        prefix, no de-quantised prefix, no cat. With an FP8 cache the
+        chunk's own rows are then read from the cache, hence quantised, as
+        a single-token step reads its own row; the route above attends on
+        the chunk's fresh bf16 rows."""
         B, T, C = x.shape
         if (dec is not None and T == 1
                 and self.attention_impl == AttentionImplementation.HIP_FLASH):
@@ -270,6 +280,16 @@ class CausalSelfAttention(nn.Module):
             cos, sin = rope_cos[pos:pos + T], rope_sin[pos:pos + T]
             q = rope_apply(q, cos, sin)
             k = rope_apply(k, cos, sin)
+        if dec is not None:   # T > 1: the multi-token decode kernels
+            if scales is None:
+                cache_k[:, pos:pos + T] = k
+                cache_v[:, pos:pos + T] = v
+                y = decode_attention(q, cache_k, cache_v, dec[1])
+            else:
+                kv_quantize_store(k, v, cache_k, cache_v, *scales, pos)
+                y = decode_attention(q, cache_k, cache_v, dec[1],
+                                     k_scale=scales[0], v_scale=scales[1])
+            return lin(self.c_proj, y.reshape(B, T, C))
         if scales is None:
             cache_k[:, pos:pos + T] = k
             cache_v[:, pos:pos + T] = v
@@ -530,7 +550,11 @@ class GPT2LLM(NNModel):
 
         A single-token step on the GPU with the HIP attention takes the
         decode route (`_decode_step`) unless `set_decode_attention(False)` /
-        MA_DECODE_ATTN=0 restores the route below."""
+        MA_DECODE_ATTN=0 restores the route below. Under the same
+        conditions a step of 2 <= T <= `ops.decode_chunk_tokens()` tokens
+        at pos > 0 attends through the multi-token decode kernels
+        (`set_decode_chunk_tokens` / MA_DECODE_CHUNK_TOKENS; 0, the
+        default, sends none there)."""
         input_ids = inputs[self.sample_key]
         B, T = input_ids.shape
         pos = cache.pos
@@ -538,6 +562,17 @@ class GPT2LLM(NNModel):
             raise ValueError(f"KV cache overflow: {pos}+{T} > {cache.max_len}")
         if T == 1 and self._decode_route(input_ids):
             return self._decode_step(input_ids, cache)
+        dec = {}
+        if 2 <= T <= decode_chunk_tokens() and pos > 0 \
+                and self._decode_route(input_ids):
+            if self._sharded_forwards():
+                raise NotImplementedError(
+                    "forward_cached: multi-token decode attention "
+                    "(set_decode_chunk_tokens) is not supported on a model "
+                    "whose block forwards are sharded (tensor or context "
+                    "parallelism); set it to 0 or use the plain model.")
+            cache.lens_dev.fill_(pos + T)   # once per call, for every layer
+            dec = {"dec": (cache.pos_dev, cache.lens_dev)}
         x = self.wte(input_ids)
         if self.wpe is not None:
             p = torch.arange(pos, pos + T, dtype=torch.long,
@@ -547,7 +582,7 @@ class GPT2LLM(NNModel):
         for i, block in enumerate(self.blocks):
             x = block.forward_cached(x, rope_cos, rope_sin,
                                      cache.k[i], cache.v[i], pos,
-                                     **cache.scales(i))
+                                     **dec, **cache.scales(i))
         cache.pos = pos + T
         cache.pos_dev.fill_(cache.pos)
         x = self.lm_head_norm(x)

@@ -11,7 +11,9 @@ torch SDPA/LayerNorm/CE/AdamW) with hand-written gfx950 HIP kernels:
                           e4m3 KV cache with per-(token, kv head) power-of-two
                           scales (quantize_kv_fp8, kv_quantize_store, and
                           k_scale / v_scale on the two decode ops): D + 4
-                          bytes per cached row instead of 2 D
+                          bytes per cached row instead of 2 D; MFMA split-KV
+                          attention of a few new tokens per row over either
+                          cache format (decode_attention with T >= 2)
 - K3  skinny_linear     : M <= 8 decode GEMM streaming bf16 or weight-only
                           e4m3 weights straight to registers
 - K3  skinny_linear_mfma: the same for M <= 32 on the matrix cores (MFMA),
@@ -47,11 +49,13 @@ from modalities_amd.ops.attention import document_starts, flash_attention  # noq
 from modalities_amd.ops.attention import (  # noqa: F401
     decode_attention,
     decode_attention_enabled,
+    decode_chunk_tokens,
     decode_rope_append,
     dequantize_kv_fp8,
     kv_quantize_store,
     quantize_kv_fp8,
     set_decode_attention,
+    set_decode_chunk_tokens,
 )
 from modalities_amd.ops.adamw import fused_adamw_step  # noqa: F401
 from modalities_amd.ops.decode_linear import (  # noqa: F401

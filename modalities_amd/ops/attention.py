@@ -42,7 +42,14 @@ head) [B, Lmax, Hkv] -- D + 4 bytes per row instead of 2 D. `quantize_kv_fp8`
 store, and `decode_rope_append` / `decode_attention` take the scales as
 k_scale / v_scale next to the code caches. scale * code is exact in bf16, so
 a bf16 cache of de-quantised values is an exact reference for the FP8 route
-(up to summation order); the CPU route is that expression in torch."""
+(up to summation order); the CPU route is that expression in torch.
+
+Multi-token steps (csrc/attention_decode_chunk.hip): `decode_attention` with
+T >= 2 query tokens per row (a speculative-decoding verify step, the next
+turn of a cached chat, a chunk of a chunked prefill) runs an MFMA split-KV
+kernel that reads either cache format in place, once for all T * (Hq / Hkv)
+query rows of a kv head. `set_decode_chunk_tokens` / MA_DECODE_CHUNK_TOKENS
+is the largest T the model sends there (0, the default: none)."""
 
 import math
 import os
@@ -432,6 +439,29 @@ def decode_attention_enabled() -> bool:
     return _DECODE_ATTN
 
 
+_DECODE_CHUNK_TOKENS = int(os.environ.get("MA_DECODE_CHUNK_TOKENS", "0"))
+if _DECODE_CHUNK_TOKENS < 0:
+    raise ValueError(f"MA_DECODE_CHUNK_TOKENS must be >= 0, got "
+                     f"{_DECODE_CHUNK_TOKENS}")
+
+
+def set_decode_chunk_tokens(n: int) -> None:
+    """The largest number of new tokens T for which a multi-token step of
+    `GPT2LLM.forward_cached` at pos > 0 attends through the multi-token
+    decode kernels (`decode_attention` with T >= 2) instead of the prefill
+    kernel on a copy of the prefix. 0 (the default) sends none there.
+    MA_DECODE_CHUNK_TOKENS sets the initial value."""
+    global _DECODE_CHUNK_TOKENS
+    if not isinstance(n, int) or isinstance(n, bool) or n < 0:
+        raise ValueError(f"set_decode_chunk_tokens: n must be an integer "
+                         f">= 0, got {n!r}")
+    _DECODE_CHUNK_TOKENS = n
+
+
+def decode_chunk_tokens() -> int:
+    return _DECODE_CHUNK_TOKENS
+
+
 def _check_index_arg(name, t, ref, B):
     if not isinstance(t, torch.Tensor) or t.dtype != torch.int32:
         raise TypeError(f"{name} must be an int32 tensor")
@@ -570,8 +600,9 @@ def kv_quantize_store(k: torch.Tensor, v: torch.Tensor,
 
 
 def _check_decode_args(q, k_cache, v_cache, kv_lens):
-    if q.dim() != 4 or q.shape[1] != 1:
-        raise ValueError(f"q must be [B, 1, Hq, D], got {tuple(q.shape)}")
+    if q.dim() != 4 or q.shape[1] < 1:
+        raise ValueError(f"q must be [B, T, Hq, D] with T >= 1, got "
+                         f"{tuple(q.shape)}")
     if k_cache.dim() != 4 or k_cache.shape != v_cache.shape:
         raise ValueError("k_cache and v_cache must be [B, Lmax, Hkv, D] of "
                          f"one shape, got {tuple(k_cache.shape)} and "
@@ -592,14 +623,17 @@ def _check_decode_args(q, k_cache, v_cache, kv_lens):
 
 def _decode_attention_ref(q, k_cache, v_cache, kv_lens):
     """Plain fp32 reference, one batch row at a time (reads the lengths on
-    the host)."""
-    Lmax = k_cache.shape[1]
+    the host). Query t of T sees the rows j < n - (T - 1 - t); the queries
+    that see none stay zero."""
+    Lmax, T = k_cache.shape[1], q.shape[1]
     o = torch.zeros_like(q)
     for b, n in enumerate(kv_lens.tolist()):
         n = min(max(n, 0), Lmax)
+        t0 = max(T - n, 0)   # the first query with a visible row
         if n > 0:
-            o[b:b + 1] = _attention_ref(q[b:b + 1], k_cache[b:b + 1, :n],
-                                        v_cache[b:b + 1, :n], causal=True)
+            o[b:b + 1, t0:] = _attention_ref(
+                q[b:b + 1, t0:], k_cache[b:b + 1, :n], v_cache[b:b + 1, :n],
+                causal=True)
     return o
 
 
@@ -617,27 +651,37 @@ def decode_attention(q: torch.Tensor, k_cache: torch.Tensor,
                      v_cache: torch.Tensor, kv_lens: torch.Tensor,
                      k_scale: Optional[torch.Tensor] = None,
                      v_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """Single-token attention over a KV cache. q: [B,1,Hq,D] (rows may be
-    strided); k_cache, v_cache: [B,Lmax,Hkv,D], read in place through their
-    strides; kv_lens: contiguous int32 [B] on q's device. Row b attends to
-    cache rows 0 .. kv_lens[b]-1 (clamped to [0, Lmax]; 0 gives zeros) and
-    nothing at or beyond the length is read. Returns o [B,1,Hq,D].
-    D in {64, 80, 128}; inference only (no autograd).
+    """Attention of T >= 1 new tokens per row over a KV cache. q: [B,T,Hq,D]
+    (heads contiguous; token and batch strides free, e.g. a view into the
+    fused-QKV output); k_cache, v_cache: [B,Lmax,Hkv,D], read in place
+    through their strides; kv_lens: contiguous int32 [B] on q's device.
+    kv_lens[b] (clamped to [0, Lmax]) counts the valid cache rows of row b
+    including the T new ones, which the caller has stored; query t attends
+    to cache rows j < kv_lens[b] - (T - 1 - t), so T == 1 sees rows
+    0 .. kv_lens[b]-1. A query that sees no row gives zeros, and nothing at
+    or beyond the length is read. Returns o [B,T,Hq,D].
+    D in {64, 80, 128}; inference only (no autograd). On the GPU T == 1
+    takes the split-KV decode kernels, T >= 2 the MFMA multi-token ones
+    (csrc/attention_decode_chunk.hip).
 
     FP8 cache: k_cache, v_cache hold float8_e4m3fn codes and k_scale,
     v_scale their fp32 [B,Lmax,Hkv] scales (`quantize_kv_fp8`); the result
     is attention over scale * code."""
     _check_decode_args(q, k_cache, v_cache, kv_lens)
+    multi = q.shape[1] > 1
     if _check_cache_scales(k_cache, v_cache, k_scale, v_scale):
         if use_hip(q, k_cache, v_cache, kv_lens, k_scale, v_scale):
-            o, _ = hip_ext().decode_attn_fp8_fwd(q, k_cache, k_scale, v_cache,
-                                                 v_scale, kv_lens)
+            fwd = hip_ext().decode_attn_chunk_fp8_fwd if multi \
+                else hip_ext().decode_attn_fp8_fwd
+            o, _ = fwd(q, k_cache, k_scale, v_cache, v_scale, kv_lens)
             return o
         return _decode_attention_ref(
             q, _dequantize_prefix(k_cache, k_scale, kv_lens),
             _dequantize_prefix(v_cache, v_scale, kv_lens), kv_lens)
     if use_hip(q, k_cache, v_cache, kv_lens):
-        o, _ = hip_ext().decode_attn_fwd(q, k_cache, v_cache, kv_lens)
+        fwd = hip_ext().decode_attn_chunk_fwd if multi \
+            else hip_ext().decode_attn_fwd
+        o, _ = fwd(q, k_cache, v_cache, kv_lens)
         return o
     return _decode_attention_ref(q, k_cache, v_cache, kv_lens)
 

@@ -28,6 +28,7 @@ SOURCES = [
     "attention_bwd.hip",
     "attention_v2.hip",
     "attention_decode.hip",
+    "attention_decode_chunk.hip",
     "decode_gemv.hip",
     "decode_gemv_mfma.hip",
     "sample_logits.hip",
