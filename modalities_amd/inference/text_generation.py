@@ -12,12 +12,13 @@ captured into a hipGraph (`DecodeGraph`) and replayed per token: the eager
 launch chain of a step is paid once. `use_decode_graph=False` opts out; a
 capture that fails falls back to the eager step.
 
-`decode_weight_format` ("fp8_e4m3" or "bf16"; default None = off) has the
+`decode_weight_format` ("fp8_e4m3", "bf16" or "mxfp4"; default None = off) has the
 model build its decode weights (GPT2LLM.prepare_decode_weights) before the
 prefill: the single-token steps of a batch of at most 32, captured or eager,
 then run their linears through the in-tree skinny GEMMs (the VALU kernel up
 to batch 8, the MFMA kernel for batch 9..32), on weight-only FP8 for
-"fp8_e4m3".
+"fp8_e4m3"; "mxfp4" runs every such batch through the MXFP4 MFMA kernel on
+4-bit microscaled weights (0.53 bytes per weight).
 
 `kv_cache_format` ("fp8_e4m3"; default None = a cache in the model's dtype)
 has the model allocate an e4m3 KV cache (GPT2LLM.new_kv_cache(kv_format=...)):

@@ -648,11 +648,21 @@ class GPT2LLM(NNModel):
         `ops.skinny_linear` up to batch 8, through `ops.skinny_linear_mfma`
         for batch 9..32 on the GPU; a layer whose in_features is no multiple
         of 16, any larger batch, and a batch above 8 on the CPU keep
-        F.linear. Prefill,
+        F.linear. `fmt` "mxfp4" (OCP microscaling FP4: e2m1 codes and one
+        power-of-two scale byte per 32 inputs, 0.53 bytes per weight) runs
+        every batch of 1..32 through `ops.skinny_linear_mxfp4`, one MFMA
+        kernel (on the CPU: torch on the de-quantized weight); a layer whose
+        in_features is no multiple of 32 keeps F.linear. 4-bit weights cost
+        accuracy that e4m3 does not: measure the model before relying on it.
+        Speed (2.7B model, profiles/decode_gemv.md, "MXFP4 kernel", one
+        run): no gain over "fp8_e4m3" at batch 1 (a 4 % loss at context
+        512), 1.16-1.27x over unset at batch 16, 1.02-1.04x at batch 32;
+        per GEMM a tie with hipBLASLt at W_2, M = 32. Prefill,
         `forward`, training and the state dict are untouched.
 
         The bf16 weights stay resident (prefill needs them), so "fp8_e4m3"
-        adds half the linears' bf16 bytes to the model's footprint. Call it
+        adds half the linears' bf16 bytes to the model's footprint and
+        "mxfp4" a good quarter. Call it
         on the device and in the dtype the model decodes in; `train()`,
         `load_state_dict` and `clear_decode_weights` drop the copies."""
         if fmt not in DECODE_WEIGHT_FORMATS:
@@ -672,7 +682,7 @@ class GPT2LLM(NNModel):
                     "full); prepare the plain model instead.")
         self.clear_decode_weights()
         for lin in lins:
-            if skinny_eligible(lin.in_features):
+            if skinny_eligible(lin.in_features, fmt):
                 set_prepared(lin, prepare_linear(lin.weight, lin.bias, fmt))
         for block in self.blocks:
             block.decode_weights = True

@@ -18,6 +18,11 @@ torch SDPA/LayerNorm/CE/AdamW) with hand-written gfx950 HIP kernels:
                           e4m3 weights straight to registers
 - K3  skinny_linear_mfma: the same for M <= 32 on the matrix cores (MFMA),
                           e4m3 widened to bf16 in registers
+- K3  skinny_linear_mxfp4: M <= 32 decode GEMM on MXFP4 weights (e2m1 codes,
+                          one e8m0 scale per 32 k; 0.53 bytes per weight):
+                          v_cvt_scalef32_pk_bf16_fp4 widens a byte to two
+                          scaled bf16 values that feed the MFMA directly
+                          (quantize_weight_mxfp4 / dequantize_weight_mxfp4)
 - K3  sample_logits     : temperature / top-k / top-p token sampler on the
                           logits row, radix selects instead of a sort; one
                           launch, capturable into the decode graph
@@ -59,9 +64,12 @@ from modalities_amd.ops.attention import (  # noqa: F401
 )
 from modalities_amd.ops.adamw import fused_adamw_step  # noqa: F401
 from modalities_amd.ops.decode_linear import (  # noqa: F401
+    dequantize_weight_mxfp4,
     quantize_weight_fp8,
+    quantize_weight_mxfp4,
     set_decode_mfma_min_rows,
     skinny_linear,
     skinny_linear_mfma,
+    skinny_linear_mxfp4,
 )
 from modalities_amd.ops.sampling import sample_logits  # noqa: F401

@@ -31,6 +31,7 @@ SOURCES = [
     "attention_decode_chunk.hip",
     "decode_gemv.hip",
     "decode_gemv_mfma.hip",
+    "decode_gemv_fp4.hip",
     "sample_logits.hip",
     "bindings.cpp",
 ]

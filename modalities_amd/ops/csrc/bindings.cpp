@@ -165,6 +165,10 @@ torch::Tensor skinny_linear_mfma(torch::Tensor x, torch::Tensor w,
                                  c10::optional<torch::Tensor> bias,
                                  long rt, long ksplit);
 long skinny_linear_mfma_max_m();
+torch::Tensor skinny_linear_mxfp4(torch::Tensor x, torch::Tensor codes,
+                                  torch::Tensor scales,
+                                  c10::optional<torch::Tensor> bias, long rt);
+long skinny_linear_mxfp4_scale_steps(long K);
 void sample_logits(torch::Tensor logits, torch::Tensor u,
                    torch::Tensor out_ids, double temperature, long top_k,
                    double top_p);
@@ -392,6 +396,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("ksplit") = 0);
   m.def("skinny_linear_mfma_max_m", &skinny_linear_mfma_max_m,
         "largest batch (rows of x) skinny_linear_mfma takes");
+  m.def("skinny_linear_mxfp4", &skinny_linear_mxfp4,
+        "y [M,N] bf16 = x [M,K] bf16 . W^T for 1 <= M <= 32, K % 32 == 0, W in "
+        "MXFP4: codes uint8 [N,K/2] (low nibble first), scales uint8 "
+        "[N,8,4,steps] (e8m0, packed per wave, k-group and step); bias is "
+        "bf16 [N] or None; rt = 1, 2 or 4 row tiles of 16 per workgroup",
+        py::arg("x"), py::arg("codes"), py::arg("scales"),
+        py::arg("bias") = py::none(), py::arg("rt") = 1);
+  m.def("skinny_linear_mxfp4_scale_steps", &skinny_linear_mxfp4_scale_steps,
+        "steps per wave in the packed scale layout of skinny_linear_mxfp4 "
+        "for a given K");
   m.def("sample_logits", &sample_logits,
         "temperature / top-k / top-p sampling of one id per logits row "
         "(bf16 or fp32 [B, V], row-strided) with u fp32 [B] in [0, 1), "

@@ -36,6 +36,25 @@ a Linear's weight, and the call that takes it for a single-token step: up to
 `skinny_linear_mfma`.
 `set_decode_mfma_min_rows` / MA_DECODE_MFMA_MIN_M move that border down for
 A/B.
+
+MXFP4 (`quantize_weight_mxfp4`, `skinny_linear_mxfp4`, decode weight format
+"mxfp4"): OCP microscaling FP4, 0.53 bytes per weight. e2m1 codes (sign, two
+exponent bits, one mantissa bit: +-{0, 0.5, 1, 1.5, 2, 3, 4, 6}), two per
+byte with k = 2j in the low nibble of byte j and k = 2j + 1 in the high one,
+and one e8m0 scale byte (2^(byte - 127)) per block of 32 consecutive k:
+
+    e = ceil(log2(amax_block / 6)) clamped to [-125, 125],  byte = e + 127
+    code = e2m1(w / 2^e)             (nearest, ties to the even mantissa bit)
+
+The block's largest value lands in (3, 6] (6 is the largest e2m1 value), so
+nothing saturates; that is the project's ceil rule, not the floor-and-
+saturate rule of the OCP text. A zero block gets byte 127; the clamp keeps
+0.5 * 2^e and 6 * 2^e normal bf16 values; the NaN byte 0xFF is never
+produced. A code times a power of two is exact in bf16, so the de-quantized
+model on the bf16 route is an exact reference here too.
+`skinny_linear_mxfp4` (csrc/decode_gemv_fp4.hip) is one MFMA kernel for
+1 <= M <= 32: gfx950 widens a byte to two scaled bf16 values in one
+instruction, half a VALU op per weight whatever M is.
 """
 
 import os
@@ -56,7 +75,21 @@ SKINNY_MFMA_MAX_M = 32
 # profiles/decode_gemv.md).
 SKINNY_MFMA_FILL_WGS = 192
 SKINNY_K_MULTIPLE = 16
-DECODE_WEIGHT_FORMATS = ("fp8_e4m3", "bf16")
+DECODE_WEIGHT_FORMATS = ("fp8_e4m3", "bf16", "mxfp4")
+MXFP4_BLOCK = 32
+MXFP4_MAX = 6.0
+MXFP4_VALUES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)   # by code & 7
+MXFP4_SCALE_BIAS = 127
+MXFP4_MAX_EXP = 125
+# skinny_linear_mxfp4: a workgroup owns 16 * RT weight rows, RT in (4, 2, 1):
+# the largest that still leaves this many workgroups (measured: RT = 4 wins
+# with 216 and loses with 120, RT = 2 wins with 240 and loses with 80;
+# profiles/decode_gemv.md, "RT A/B"). The packed scale layout is the
+# kernel's: [N, waves, k-groups, steps per wave].
+SKINNY_FP4_FILL_WGS = 192
+SKINNY_FP4_WAVES = 8
+SKINNY_FP4_GROUPS = 4
+SKINNY_FP4_QUAD = 4
 
 
 def quantize_weight_fp8(w: torch.Tensor,
@@ -94,6 +127,165 @@ def quantize_weight_fp8(w: torch.Tensor,
     q = (wf / scale[:, None]).clamp(-E4M3_MAX, E4M3_MAX)
     wq = q.to(torch.float8_e4m3fn).contiguous()
     return wq, scale.contiguous()
+
+
+def quantize_weight_mxfp4(w: torch.Tensor
+                          ) -> tuple[torch.Tensor, torch.Tensor]:
+    """w [N, K] (bf16 or fp32), K % 32 == 0 -> (codes uint8 [N, K/2], scales
+    uint8 [N, K/32]) in the MXFP4 layout of the module docstring. Pure torch,
+    bit-identical on CPU and GPU. Non-finite weights raise ValueError."""
+    if not isinstance(w, torch.Tensor) or w.dim() != 2:
+        raise ValueError("quantize_weight_mxfp4: w must be a [N, K] tensor")
+    if w.dtype not in (torch.bfloat16, torch.float32):
+        raise TypeError(f"quantize_weight_mxfp4: w must be bf16 or fp32, got "
+                        f"{w.dtype}")
+    N, K = w.shape
+    if K < MXFP4_BLOCK or K % MXFP4_BLOCK != 0:
+        raise ValueError(f"quantize_weight_mxfp4: K must be a positive "
+                         f"multiple of {MXFP4_BLOCK}, got {K}")
+    wf = w.detach().float().reshape(N, K // MXFP4_BLOCK, MXFP4_BLOCK)
+    if not bool(torch.isfinite(wf).all()):
+        raise ValueError("quantize_weight_mxfp4: w holds non-finite values")
+    amax = wf.abs().amax(dim=2)
+    # amax / 6 = m * 2^e with m in [0.5, 1): ceil(log2) is e, or e - 1 when
+    # the ratio is itself a power of two (m == 0.5). Exact, no log.
+    m, e = torch.frexp(amax / MXFP4_MAX)
+    e = torch.where(m == 0.5, e - 1, e)
+    e = torch.where(amax > 0, e, torch.zeros_like(e))
+    e = e.clamp(-MXFP4_MAX_EXP, MXFP4_MAX_EXP)
+    # 2^-e built from its bits (127 - e is in [2, 252]): the product is exact
+    inv = ((MXFP4_SCALE_BIAS - e).to(torch.int32) << 23).view(torch.float32)
+    a = (wf.abs() * inv[:, :, None]).clamp(max=MXFP4_MAX)
+    # nearest with ties to even on the grid of each binade: steps of 0.5
+    # below 2, of 1 below 4, of 2 up to 6 (torch.round is half-to-even)
+    step = torch.where(a < 2, 0.5, torch.where(a < 4, 1.0, 2.0))
+    q = torch.round(a / step) * step
+    # value -> code: 0, .5, 1, 1.5 are 2q; 2, 3 are q + 2; 4, 6 are q/2 + 4
+    code = torch.where(q < 2, 2 * q, torch.where(q < 4, q + 2, q / 2 + 4))
+    code = code.to(torch.uint8) | torch.signbit(wf).to(torch.uint8) * 8
+    code = code.reshape(N, K // 2, 2)
+    codes = (code[:, :, 0] | (code[:, :, 1] << 4)).contiguous()
+    scales = (e + MXFP4_SCALE_BIAS).to(torch.uint8).contiguous()
+    return codes, scales
+
+
+def mxfp4_scale_steps(K: int) -> int:
+    """Steps per wave the packed scale layout holds: a wave's share of the
+    ceil(K / 128) wave steps, rounded up to whole dwords."""
+    steps = -(-K // (MXFP4_BLOCK * SKINNY_FP4_GROUPS))
+    per_wave = -(-steps // SKINNY_FP4_WAVES)
+    return -(-per_wave // SKINNY_FP4_QUAD) * SKINNY_FP4_QUAD
+
+
+def pack_mxfp4_scales(scales: torch.Tensor) -> torch.Tensor:
+    """scales uint8 [N, K/32] -> uint8 [N, 8, 4, T] in the order the kernel
+    consumes them: [n, w, g, t] is the scale of block 4 * (w + 8 t) + g, so a
+    lane's next four steps are one dword; blocks past K/32 hold 127 (2^0)."""
+    N, C = scales.shape
+    T = mxfp4_scale_steps(C * MXFP4_BLOCK)
+    per_t = SKINNY_FP4_WAVES * SKINNY_FP4_GROUPS
+    padded = scales.new_full((N, T * per_t), MXFP4_SCALE_BIAS)
+    padded[:, :C] = scales
+    return padded.view(N, T, SKINNY_FP4_WAVES, SKINNY_FP4_GROUPS) \
+        .permute(0, 2, 3, 1).contiguous()
+
+
+def _unpacked_mxfp4_scales(scales: torch.Tensor, C: int) -> torch.Tensor:
+    if scales.dim() == 2:
+        return scales
+    return scales.permute(0, 3, 1, 2).reshape(scales.shape[0], -1)[:, :C]
+
+
+def dequantize_weight_mxfp4(codes: torch.Tensor,
+                            scales: torch.Tensor) -> torch.Tensor:
+    """(codes uint8 [N, K/2], scales uint8 [N, K/32] or their packed form)
+    -> bf16 [N, K], exactly code * 2^(scale - 127)."""
+    N, half = codes.shape
+    C = half * 2 // MXFP4_BLOCK
+    sc = _unpacked_mxfp4_scales(scales, C)
+    if tuple(sc.shape) != (N, C):
+        raise ValueError(f"dequantize_weight_mxfp4: scales must be [N, K/32] "
+                         f"= {(N, C)}, got {tuple(sc.shape)}")
+    nib = torch.stack((codes & 0xF, codes >> 4), dim=2).reshape(N, 2 * half)
+    mag = torch.tensor(MXFP4_VALUES, device=codes.device)[(nib & 7).long()]
+    val = torch.where((nib & 8) != 0, -mag, mag)
+    two_e = (sc.to(torch.int32) << 23).view(torch.float32)   # as the kernel
+    val = val.view(N, C, MXFP4_BLOCK) * two_e[:, :, None]
+    return val.reshape(N, 2 * half).to(torch.bfloat16)
+
+
+def _fp4_row_tiles(N: int) -> int:
+    for rt in (4, 2):
+        if -(-N // (16 * rt)) >= SKINNY_FP4_FILL_WGS:
+            return rt
+    return 1
+
+
+def skinny_linear_mxfp4(x: torch.Tensor, codes: torch.Tensor,
+                        scales: torch.Tensor,
+                        bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """y [M, N] bf16 = x [M, K] . dequantize_weight_mxfp4(codes, scales)^T
+    (+ bias[n]) for 1 <= M <= 32, K % 32 == 0: fp32 products and sums, one
+    rounding. x: bf16, unit stride in K, rows may be strided. codes: uint8
+    [N, K/2]; scales: uint8 [N, K/32], or `pack_mxfp4_scales` of it (what
+    `prepare_linear` keeps; the plain layout is packed on every call). A
+    row's result does not depend on M or on where the row sits in x.
+    Measured once on the 2.7B shapes (profiles/decode_gemv.md, "MXFP4
+    kernel"): against the e4m3 kernels it ties at M = 1 (lm_head 1.12x) and
+    wins 1.1-2.5x at M = 8..32; against hipBLASLt on bf16 it wins 1.4-2.5x
+    up to M = 16 and 1.08-1.25x at M = 32, where W_2 only ties (1.01x).
+    Inference only (no autograd)."""
+    for name, t in (("x", x), ("codes", codes), ("scales", scales)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"skinny_linear_mxfp4: {name} must be a tensor")
+    if x.dtype != torch.bfloat16:
+        raise TypeError(f"skinny_linear_mxfp4: x must be bf16, got {x.dtype}")
+    if codes.dtype != torch.uint8 or scales.dtype != torch.uint8:
+        raise TypeError("skinny_linear_mxfp4: codes and scales must be uint8")
+    if x.dim() != 2 or codes.dim() != 2:
+        raise ValueError("skinny_linear_mxfp4: x must be [M, K] and codes "
+                         f"[N, K/2], got {tuple(x.shape)} and "
+                         f"{tuple(codes.shape)}")
+    M, K = x.shape
+    N = codes.shape[0]
+    if not 1 <= M <= SKINNY_MFMA_MAX_M:
+        raise ValueError(f"skinny_linear_mxfp4: M must be in [1, "
+                         f"{SKINNY_MFMA_MAX_M}], got {M}")
+    if K < MXFP4_BLOCK or K % MXFP4_BLOCK != 0 or codes.shape[1] * 2 != K:
+        raise ValueError(f"skinny_linear_mxfp4: K must be a positive multiple "
+                         f"of {MXFP4_BLOCK} shared by x and codes, got {K} "
+                         f"and {codes.shape[1] * 2}")
+    if N < 1 or not codes.is_contiguous():
+        raise ValueError("skinny_linear_mxfp4: codes must be contiguous with "
+                         "at least one row")
+    want = ((N, K // MXFP4_BLOCK), (N, SKINNY_FP4_WAVES, SKINNY_FP4_GROUPS,
+                                    mxfp4_scale_steps(K)))
+    if tuple(scales.shape) not in want:
+        raise ValueError(f"skinny_linear_mxfp4: scales must be [N, K/32] = "
+                         f"{want[0]} or packed {want[1]}, got "
+                         f"{tuple(scales.shape)}")
+    if x.stride(1) != 1:
+        raise ValueError("skinny_linear_mxfp4: x must have unit stride in K")
+    if bias is not None:
+        if not isinstance(bias, torch.Tensor) or bias.dtype != torch.bfloat16:
+            raise TypeError("skinny_linear_mxfp4: bias must be a bf16 tensor "
+                            "or None")
+        if tuple(bias.shape) != (N,) or not bias.is_contiguous():
+            raise ValueError(f"skinny_linear_mxfp4: bias must be contiguous "
+                             f"[N] = {(N,)}, got {tuple(bias.shape)}")
+    for name, t in (("codes", codes), ("scales", scales), ("bias", bias)):
+        if t is not None and t.device != x.device:
+            raise ValueError(f"skinny_linear_mxfp4: {name} is on {t.device}, "
+                             f"x on {x.device}")
+    if use_hip(x, codes, scales, bias):
+        if (M > 1 and x.stride(0) % 8 != 0) or x.data_ptr() % 16 != 0:
+            x = x.contiguous()   # the kernel reads x in 16-byte pieces
+        if scales.dim() == 2:
+            scales = pack_mxfp4_scales(scales)
+        return hip_ext().skinny_linear_mxfp4(x, codes, scales.contiguous(),
+                                             bias, _fp4_row_tiles(N))
+    return _skinny_linear_ref(x, dequantize_weight_mxfp4(codes, scales), None,
+                              bias)
 
 
 def _check_skinny_args(x, w, scale, bias, max_m=SKINNY_MAX_M):
@@ -226,16 +418,17 @@ def decode_mfma_min_rows() -> int:
 
 
 class PreparedLinear(NamedTuple):
-    """Decode-time copy of one Linear: w [N, K] in `fmt`, its scale (e4m3
-    only) and the bias in bf16."""
+    """Decode-time copy of one Linear: w [N, K] in `fmt`, its scale (e4m3:
+    fp32 [N]; mxfp4: w holds the uint8 codes [N, K/2] and scale the packed
+    e8m0 bytes of `pack_mxfp4_scales`; bf16: None) and the bias in bf16."""
     w: torch.Tensor
     scale: Optional[torch.Tensor]
     bias: Optional[torch.Tensor]
 
 
-def skinny_eligible(in_features: int) -> bool:
-    return in_features >= SKINNY_K_MULTIPLE \
-        and in_features % SKINNY_K_MULTIPLE == 0
+def skinny_eligible(in_features: int, fmt: Optional[str] = None) -> bool:
+    mult = MXFP4_BLOCK if fmt == "mxfp4" else SKINNY_K_MULTIPLE
+    return in_features >= mult and in_features % mult == 0
 
 
 def prepare_linear(weight: torch.Tensor, bias: Optional[torch.Tensor],
@@ -250,6 +443,9 @@ def prepare_linear(weight: torch.Tensor, bias: Optional[torch.Tensor],
         return PreparedLinear(w.to(torch.bfloat16).contiguous(), None, b)
     if w.dtype not in (torch.bfloat16, torch.float32):
         w = w.float()
+    if fmt == "mxfp4":
+        codes, scales = quantize_weight_mxfp4(w)
+        return PreparedLinear(codes, pack_mxfp4_scales(scales), b)
     wq, scale = quantize_weight_fp8(w)
     return PreparedLinear(wq, scale, b)
 
@@ -277,11 +473,20 @@ def step_linear(lin: torch.nn.Module, x: torch.Tensor) -> torch.Tensor:
     9 <= B <= 32 (`set_decode_mfma_min_rows` moves the border down);
     through the module itself (F.linear on the resident weight) otherwise.
     The MFMA route is the device's: on the CPU, where there is no kernel to
-    reach, a step of more than 8 rows stays on F.linear as it always has."""
+    reach, a step of more than 8 rows stays on F.linear as it always has.
+    An MXFP4 copy (uint8 codes) sends 1 <= B <= 32 to `skinny_linear_mxfp4`,
+    on the CPU too (there the torch expression on the de-quantized weight)."""
     prep = lin.__dict__.get(_ATTR)
     if prep is None:
         return lin(x)
     rows = x.numel() // x.shape[-1]
+    if prep.w.dtype == torch.uint8:
+        if not 1 <= rows <= SKINNY_MFMA_MAX_M or x.dtype != torch.bfloat16 \
+                or x.device != prep.w.device:
+            return F.linear(x, lin.weight, lin.bias)
+        y = skinny_linear_mxfp4(x.reshape(rows, x.shape[-1]), prep.w,
+                                prep.scale, prep.bias)
+        return y.view(*x.shape[:-1], prep.w.shape[0])
     mfma = x.is_cuda and rows >= _MFMA_MIN_ROWS
     max_rows = SKINNY_MFMA_MAX_M if mfma else SKINNY_MAX_M
     if rows > max_rows or rows < 1 or x.dtype != torch.bfloat16 \

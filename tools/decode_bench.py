@@ -3,7 +3,7 @@ re-forward on the flagship 2.7B shape (GPU).
 
     PYTHONPATH=. python tools/decode_bench.py [--ctx 512 2048 3968]
         [--batch 1 [16 32 ...]] [--impl {flash,split,graph}]
-        [--weights {off,bf16,fp8_e4m3}] [--kv-format {bf16,fp8_e4m3}]
+        [--weights {off,bf16,fp8_e4m3,mxfp4} ...] [--kv-format {bf16,fp8_e4m3}]
         [--kv-logit-diff]
 
 --impl picks the route of the cached single-token step: `flash` is the
@@ -16,7 +16,9 @@ forward_cached), `graph` the same step captured into a hipGraph and replayed
 default) leaves the linears on F.linear / hipBLASLt, `bf16` and `fp8_e4m3`
 prepare them (GPT2LLM.prepare_decode_weights) for the in-tree skinny GEMMs
 (the VALU kernel up to batch 8, the MFMA kernel for batch 9..32), on the bf16
-weights or on weight-only FP8. --batch takes one or more batch sizes; each
+weights or on weight-only FP8; `mxfp4` prepares MXFP4 weights for the MXFP4
+MFMA kernel (every batch up to 32). Several values run one after the other on
+the same model, one line each. --batch takes one or more batch sizes; each
 runs every --ctx.
 
 --kv-format fp8_e4m3 decodes on an e4m3 KV cache (new_kv_cache(kv_format=));
@@ -125,10 +127,10 @@ def main():
     ap.add_argument("--batch", type=int, nargs="+", default=[1])
     ap.add_argument("--impl", choices=["flash", "split", "graph"],
                     default="split")
-    ap.add_argument("--weights", choices=["off", "bf16", "fp8_e4m3"],
-                    default="off")
+    ap.add_argument("--weights", nargs="+", default=["off"],
+                    choices=["off", "bf16", "fp8_e4m3", "mxfp4"])
     ap.add_argument("--logit-error", action="store_true",
-                    help="with --weights bf16/fp8_e4m3: also print the "
+                    help="with --weights bf16/fp8_e4m3/mxfp4: also print the "
                          "error of a step's logits against the bf16 route")
     ap.add_argument("--kv-format", choices=["bf16", "fp8_e4m3"],
                     default="bf16")
@@ -139,8 +141,15 @@ def main():
                     help="skip the full-context re-forward comparison")
     args = ap.parse_args()
     model, cfg = build_model()
-    if args.weights != "off":
-        model.prepare_decode_weights(args.weights)
+    for weights in args.weights:
+        model.clear_decode_weights()
+        if weights != "off":
+            model.prepare_decode_weights(weights)
+        args.weights = weights
+        run(model, cfg, args)
+
+
+def run(model, cfg, args):
     kv_format = None if args.kv_format == "bf16" else args.kv_format
     for batch in args.batch:
         for ctx in args.ctx:

@@ -7,11 +7,14 @@
   e4m3    ops.skinny_linear on the weight-only FP8 copy (half the bytes)
   mfma-bf16 / mfma-e4m3
           ops.skinny_linear_mfma (matrix cores, M <= 32) on the same two
+  mxfp4   ops.skinny_linear_mxfp4 (matrix cores, M <= 32) on the MXFP4 copy
+          (0.53 bytes per weight)
 
 for QKV, c_proj, packed W|V, W_2 and lm_head at M = 1, 8, 16 and 32, in one
 process; the VALU kernel (bf16, e4m3) only where M <= 8. `--tilings` times
 the MFMA kernel's RT x KSPLIT instantiations on the e4m3 weight instead (the
-A/B behind the shipped MFMA_GEMV_RT / MFMA_GEMV_KSPLIT).
+A/B behind the shipped MFMA_GEMV_RT / MFMA_GEMV_KSPLIT) and the MXFP4
+kernel's RT = 1, 2, 4 (the A/B behind SKINNY_FP4_FILL_WGS).
 
 A decode step streams every weight of the model once per token, so each
 weight arrives cold. To time that and not a cache-resident loop, every shape
@@ -74,10 +77,13 @@ def replay_us(g, ncalls):
 
 
 def main():
-    from modalities_amd.ops import (quantize_weight_fp8, skinny_linear,
-                                    skinny_linear_mfma)
+    from modalities_amd.ops import (dequantize_weight_mxfp4,
+                                    quantize_weight_fp8, quantize_weight_mxfp4,
+                                    skinny_linear, skinny_linear_mfma,
+                                    skinny_linear_mxfp4)
     from modalities_amd.ops.backend import hip_ext, require_hip
-    from modalities_amd.ops.decode_linear import SKINNY_MAX_M
+    from modalities_amd.ops.decode_linear import (SKINNY_MAX_M,
+                                                  pack_mxfp4_scales)
     require_hip("decode_gemv_bench")
     ap = argparse.ArgumentParser()
     ap.add_argument("--m", type=int, nargs="+", default=[1, 8, 16, 32])
@@ -99,10 +105,15 @@ def main():
             continue
         w = (torch.randn(N, K, device="cuda") * 0.02).bfloat16()
         wq, scale = quantize_weight_fp8(w)
+        w4, s4 = quantize_weight_mxfp4(w)
+        s4 = pack_mxfp4_scales(s4)
         ncopy = max(2, -(-args.cold_mb * (1 << 20) // (N * K)))   # e4m3 bytes
         ncalls = max(args.calls, ncopy)
         wb = [w.clone() for _ in range(ncopy)]
         w8 = [wq.clone() for _ in range(ncopy)]
+        # twice the copies: the MXFP4 set is as cold as the e4m3 one
+        w4 = [(w4.clone(), s4.clone()) for _ in range(2 * ncopy)]
+        ref4_w = dequantize_weight_mxfp4(*w4[0])
         for M in args.m:
             x = torch.randn(M, K, device="cuda").bfloat16()
             impls = {"blaslt": lambda i: F.linear(x, wb[i % ncopy])}
@@ -112,6 +123,10 @@ def main():
                         impls[f"rt{rt}ks{ks}"] = \
                             lambda i, rt=rt, ks=ks: hip_ext().skinny_linear_mfma(
                                 x, w8[i % ncopy], scale, None, rt, ks)
+                for rt in (1, 2, 4):
+                    impls[f"mxfp4-rt{rt}"] = \
+                        lambda i, rt=rt: hip_ext().skinny_linear_mxfp4(
+                            x, *w4[i % (2 * ncopy)], None, rt)
             else:
                 if M <= SKINNY_MAX_M:
                     impls["bf16"] = lambda i: skinny_linear(x, wb[i % ncopy])
@@ -121,6 +136,8 @@ def main():
                     x, wb[i % ncopy])
                 impls["mfma-e4m3"] = lambda i: skinny_linear_mfma(
                     x, w8[i % ncopy], scale)
+                impls["mxfp4"] = lambda i: skinny_linear_mxfp4(
+                    x, *w4[i % (2 * ncopy)])
             graphs = {k: capture(fn, ncalls) for k, fn in impls.items()}
             for g, _ in graphs.values():     # warm every graph once
                 replay_us(g, ncalls)
@@ -128,8 +145,10 @@ def main():
             # of a graph hold values only after a replay)
             ref = graphs["blaslt"][1][0].float()
             ref8 = F.linear(x, (wq.float() * scale[:, None]).bfloat16()).float()
+            ref4 = F.linear(x, ref4_w).float()
             diff = {k: (graphs[k][1][0].float()
-                        - (ref if k.endswith("bf16") else ref8)).abs().max()
+                        - (ref if k.endswith("bf16") else
+                           ref4 if k.startswith("mxfp4") else ref8)).abs().max()
                     .item() for k in impls if k != "blaslt"}
             us = {k: [] for k in impls}
             for _ in range(args.repeats):    # alternate the implementations
@@ -140,7 +159,7 @@ def main():
             for k in impls:
                 med[k] = statistics.median(us[k])
                 nbytes = N * K * (2 if k in ("blaslt", "bf16", "mfma-bf16")
-                                  else 1)
+                                  else 17 / 32 if k.startswith("mxfp4") else 1)
                 line += (f"  {k} {med[k]:7.2f} us [{min(us[k]):.2f}.."
                          f"{max(us[k]):.2f}] {nbytes / med[k] / 1e3:6.0f} GB/s")
             line += "  |" + "".join(
@@ -150,7 +169,7 @@ def main():
                                             for k, d in diff.items())
             print(line, flush=True)
             del graphs
-        del wb, w8
+        del wb, w8, w4
         torch.cuda.empty_cache()
 
 
