@@ -10,6 +10,7 @@ Attention head_dim is sized for MFMA tiles (multiples of 16; 64/128 fast)."""
 
 import math
 from enum import Enum
+from functools import partial
 from typing import Annotated, Optional
 
 import torch
@@ -29,6 +30,7 @@ from modalities_amd.ops.attention import (DECODE_HEAD_DIMS, KV_CACHE_FORMATS,
                                           kv_quantize_store)
 from modalities_amd.ops.backend import use_hip
 from modalities_amd.ops.decode_linear import (DECODE_WEIGHT_FORMATS,
+                                              decode_fused_step,
                                               prepare_linear, set_prepared,
                                               skinny_eligible, step_linear)
 from modalities_amd.ops.layer_norm import LayerNorm
@@ -224,7 +226,8 @@ class CausalSelfAttention(nn.Module):
         return self.resid_dropout(self.c_proj(y))
 
     def forward_cached(self, x, rope_cos, rope_sin, cache_k, cache_v,
-                       pos: int, dec=None, scales=None):
+                       pos: int, dec=None, scales=None, norm=None,
+                       residual=None):
         """Incremental-decode step: project the T_new tokens at absolute
         positions [pos, pos+T_new), append K/V into the preallocated cache,
         attend q against the cache prefix with q_offset=pos (the same
@@ -252,9 +255,23 @@ class CausalSelfAttention(nn.Module):
         prefix, no de-quantised prefix, no cat. With an FP8 cache the
         chunk's own rows are then read from the cache, hence quantised, as
         a single-token step reads its own row; the route above attends on
-        the chunk's fresh bf16 rows."""
+        the chunk's fresh bf16 rows.
+
+        norm / residual (the fused decode step, T == 1 only): x is the raw
+        block input, `norm` the block's attention norm and the result is
+        residual + attn(norm(x)); the norm rides on the q/k/v projections
+        and the add on c_proj (`step_linear`)."""
         B, T, C = x.shape
-        if (dec is not None and T == 1
+        if norm is not None or residual is not None:
+            assert T == 1, "norm / residual are a single-token step's"
+            lin_in = partial(step_linear, norm=norm)
+            lin_out = partial(step_linear, residual=residual)
+            if (dec is not None and self.attention_impl
+                    == AttentionImplementation.HIP_FLASH):
+                return self._forward_decode(x, rope_cos, rope_sin, cache_k,
+                                            cache_v, *dec, scales=scales,
+                                            lin_in=lin_in, lin_out=lin_out)
+        elif (dec is not None and T == 1
                 and self.attention_impl == AttentionImplementation.HIP_FLASH):
             if scales is not None:
                 return self._forward_decode(x, rope_cos, rope_sin, cache_k,
@@ -264,12 +281,14 @@ class CausalSelfAttention(nn.Module):
         kv_dim = self.head_dim * self.n_head_kv
         # a single-token step takes the prepared decode weights, if any
         lin = step_linear if T == 1 else _call_linear
+        if norm is None and residual is None:
+            lin_in = lin_out = lin
         if self.fused_qkv:
-            qkv = lin(self.qkv_attn, x)
+            qkv = lin_in(self.qkv_attn, x)
             q, k, v = qkv.split([C, kv_dim, kv_dim], dim=-1)
         else:
-            q, k, v = (lin(self.q_attn, x), lin(self.k_attn, x),
-                       lin(self.v_attn, x))
+            q, k, v = (lin_in(self.q_attn, x), lin_in(self.k_attn, x),
+                       lin_in(self.v_attn, x))
         q = q.view(B, T, self.n_head_q, self.head_dim)
         k = k.view(B, T, self.n_head_kv, self.head_dim)
         v = v.view(B, T, self.n_head_kv, self.head_dim)
@@ -289,7 +308,7 @@ class CausalSelfAttention(nn.Module):
                 kv_quantize_store(k, v, cache_k, cache_v, *scales, pos)
                 y = decode_attention(q, cache_k, cache_v, dec[1],
                                      k_scale=scales[0], v_scale=scales[1])
-            return lin(self.c_proj, y.reshape(B, T, C))
+            return lin_out(self.c_proj, y.reshape(B, T, C))
         if scales is None:
             cache_k[:, pos:pos + T] = k
             cache_v[:, pos:pos + T] = v
@@ -320,20 +339,20 @@ class CausalSelfAttention(nn.Module):
             y = torch.nn.functional.scaled_dot_product_attention(
                 qt, kt, vt, attn_mask=mask)
             y = y.transpose(1, 2)
-        return lin(self.c_proj, y.reshape(B, T, C))
+        return lin_out(self.c_proj, y.reshape(B, T, C))
 
     def _forward_decode(self, x, rope_cos, rope_sin, cache_k, cache_v,
-                        pos_dev, lens_dev, scales=None):
+                        pos_dev, lens_dev, scales=None, lin_in=step_linear,
+                        lin_out=step_linear):
         B, _, C = x.shape
         kv_dim = self.head_dim * self.n_head_kv
         if self.fused_qkv:
             # q, k, v stay row-strided views into the joint projection
-            qkv = step_linear(self.qkv_attn, x)
+            qkv = lin_in(self.qkv_attn, x)
             q, k, v = qkv.split([C, kv_dim, kv_dim], dim=-1)
         else:
-            q, k, v = (step_linear(self.q_attn, x),
-                       step_linear(self.k_attn, x),
-                       step_linear(self.v_attn, x))
+            q, k, v = (lin_in(self.q_attn, x), lin_in(self.k_attn, x),
+                       lin_in(self.v_attn, x))
         q = q.view(B, 1, self.n_head_q, self.head_dim)
         k = k.view(B, 1, self.n_head_kv, self.head_dim)
         v = v.view(B, 1, self.n_head_kv, self.head_dim)
@@ -350,7 +369,7 @@ class CausalSelfAttention(nn.Module):
                                    v_scale=scales[1])
             y = decode_attention(q, cache_k, cache_v, lens_dev,
                                  k_scale=scales[0], v_scale=scales[1])
-        return step_linear(self.c_proj, y.reshape(B, 1, C))
+        return lin_out(self.c_proj, y.reshape(B, 1, C))
 
     def _attend(self, q, k, v, doc_start=None):
         if self.attention_impl == AttentionImplementation.HIP_FLASH:
@@ -391,10 +410,14 @@ class TransformerMLP(nn.Module):
     def forward(self, x):
         return self.dropout(self.c_proj(self.gelu(self.c_fc(x))))
 
-    def forward_step(self, x):
+    def forward_step(self, x, norm=None, residual=None):
         """forward for a single-token decode step (inference: no dropout),
-        on the prepared decode weights where the linears carry them."""
-        return step_linear(self.c_proj, self.gelu(step_linear(self.c_fc, x)))
+        on the prepared decode weights where the linears carry them. With
+        `norm` / `residual` (the fused decode step) x is the raw block input
+        and the result is residual + mlp(norm(x))."""
+        return step_linear(self.c_proj,
+                           self.gelu(step_linear(self.c_fc, x, norm=norm)),
+                           residual=residual)
 
 
 class GPT2Block(nn.Module):
@@ -428,6 +451,15 @@ class GPT2Block(nn.Module):
 
     def forward_cached(self, x, rope_cos, rope_sin, cache_k, cache_v, pos,
                        dec=None, scales=None):
+        if self.decode_weights and x.shape[1] == 1 and decode_fused_step() \
+                and isinstance(self.attention_norm, RMSNorm) \
+                and isinstance(self.ffn_norm, RMSNorm):
+            # the fused decode step: norms, gate and adds ride on the GEMMs
+            # (a block with a LayerNorm stays as it is, adds included)
+            x = self.attn.forward_cached(x, rope_cos, rope_sin, cache_k,
+                                         cache_v, pos, dec=dec, scales=scales,
+                                         norm=self.attention_norm, residual=x)
+            return self.mlp.forward_step(x, norm=self.ffn_norm, residual=x)
         if scales is not None:   # FP8 cache
             x = x + self.attn.forward_cached(self.attention_norm(x), rope_cos,
                                              rope_sin, cache_k, cache_v, pos,
@@ -585,6 +617,9 @@ class GPT2LLM(NNModel):
                                      **dec, **cache.scales(i))
         cache.pos = pos + T
         cache.pos_dev.fill_(cache.pos)
+        if T == 1 and self._fused_head():
+            return {self.prediction_key: step_linear(self.lm_head, x,
+                                                     norm=self.lm_head_norm)}
         x = self.lm_head_norm(x)
         if T == 1:
             return {self.prediction_key: step_linear(self.lm_head, x)}
@@ -616,8 +651,16 @@ class GPT2LLM(NNModel):
                                      dec=dec, **cache.scales(i))
         cache.pos_dev.add_(1)
         cache.pos += 1
+        if self._fused_head():
+            return {self.prediction_key: step_linear(self.lm_head, x,
+                                                     norm=self.lm_head_norm)}
         x = self.lm_head_norm(x)
         return {self.prediction_key: step_linear(self.lm_head, x)}
+
+    def _fused_head(self) -> bool:
+        return decode_fused_step() \
+            and getattr(self, "decode_weight_format", None) is not None \
+            and isinstance(self.lm_head_norm, RMSNorm)
 
     # -- decode weights (weight-only FP8 / in-tree skinny GEMM) -----------
     def _decode_linears(self) -> list[nn.Linear]:

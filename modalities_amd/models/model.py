@@ -80,10 +80,20 @@ class SwiGLU(nn.Module):
             return self.W_2(silu_mul_joint(self.Wv(x)))
         return self.W_2(silu_mul(self.W(x), self.V(x)))
 
-    def forward_step(self, x: torch.Tensor) -> torch.Tensor:
+    def forward_step(self, x: torch.Tensor, norm=None,
+                     residual=None) -> torch.Tensor:
         """forward for a single-token decode step, on the prepared decode
         weights (GPT2LLM.prepare_decode_weights) where the linears carry
-        them."""
+        them. With `norm` / `residual` (the fused decode step) x is the raw
+        block input and the result is residual + mlp(norm(x)): the norm and
+        the gate ride on the up projection, the add on W_2."""
+        if norm is not None or residual is not None:
+            if self.packed:
+                h = step_linear(self.Wv, x, norm=norm, glu=True)
+            else:
+                h = silu_mul(step_linear(self.W, x, norm=norm),
+                             step_linear(self.V, x, norm=norm))
+            return step_linear(self.W_2, h, residual=residual)
         if self.packed:
             return step_linear(self.W_2, silu_mul_joint(step_linear(self.Wv, x)))
         return step_linear(self.W_2, silu_mul(step_linear(self.W, x),

@@ -15,7 +15,10 @@ torch SDPA/LayerNorm/CE/AdamW) with hand-written gfx950 HIP kernels:
                           attention of a few new tokens per row over either
                           cache format (decode_attention with T >= 2)
 - K3  skinny_linear     : M <= 8 decode GEMM streaming bf16 or weight-only
-                          e4m3 weights straight to registers
+                          e4m3 weights straight to registers; optionally with
+                          an RMSNorm prologue, a SwiGLU gate and a residual
+                          add fused in (norm_weight / glu / residual;
+                          set_decode_fused_step turns them on for the model)
 - K3  skinny_linear_mfma: the same for M <= 32 on the matrix cores (MFMA),
                           e4m3 widened to bf16 in registers
 - K3  skinny_linear_mxfp4: M <= 32 decode GEMM on MXFP4 weights (e2m1 codes,
@@ -64,7 +67,9 @@ from modalities_amd.ops.attention import (  # noqa: F401
 )
 from modalities_amd.ops.adamw import fused_adamw_step  # noqa: F401
 from modalities_amd.ops.decode_linear import (  # noqa: F401
+    decode_fused_step,
     dequantize_weight_mxfp4,
+    set_decode_fused_step,
     quantize_weight_fp8,
     quantize_weight_mxfp4,
     set_decode_mfma_min_rows,

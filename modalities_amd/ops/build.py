@@ -5,10 +5,12 @@ lib paths; gfx950 only. The .so lands next to this file so repo snapshots
 carry it to GPU boxes. Usage: python -m modalities_amd.ops.build
 """
 
+import os
 import subprocess
 import sys
 import sysconfig
 import tempfile
+from concurrent.futures import ThreadPoolExecutor
 from pathlib import Path
 
 import torch
@@ -30,15 +32,16 @@ SOURCES = [
     "attention_decode.hip",
     "attention_decode_chunk.hip",
     "decode_gemv.hip",
+    "decode_gemv_fused.hip",
     "decode_gemv_mfma.hip",
     "decode_gemv_fp4.hip",
     "sample_logits.hip",
     "bindings.cpp",
 ]
 
-# Compiled on their own, with packed fp32 arithmetic (v_pk_fma_f32 and kin)
-# switched off, and linked into the same library; SOURCES keep the flags
-# they were tuned and validated with.
+# Compiled with packed fp32 arithmetic (v_pk_fma_f32 and kin) switched off
+# and linked into the same library; SOURCES keep the flags they were tuned
+# and validated with.
 NO_PACKED_FP32_SOURCES = [
     "attention_decode_fp8.hip",
 ]
@@ -47,13 +50,14 @@ NO_PACKED_FP32_FLAGS = ["-Xclang", "-target-feature", "-Xclang",
 
 HEADERS = ["common.h", "attn_common.h", "attention_decode_common.h"]
 
+COMPILE_JOBS = 8   # hipcc processes at a time
+
 
 def build_extension(verbose: bool = True, arch: str = "gfx950") -> Path:
     torch_lib = Path(torch.__file__).parent / "lib"
     includes = cpp_extension.include_paths() + [sysconfig.get_paths()["include"]]
     abi = int(torch._C._GLIBCXX_USE_CXX11_ABI)
 
-    srcs = [str(CSRC / s) for s in SOURCES]
     newest_src = max((CSRC / s).stat().st_mtime
                      for s in SOURCES + NO_PACKED_FP32_SOURCES + HEADERS)
     if OUT.exists() and OUT.stat().st_mtime > newest_src:
@@ -69,15 +73,21 @@ def build_extension(verbose: bool = True, arch: str = "gfx950") -> Path:
          "-Wno-unused-result", "-fno-gpu-rdc"]
         + [f"-I{p}" for p in includes]
     )
+    # One object per source, a few at a time: most of a source's compile
+    # time is the host pass over the torch headers, which a single hipcc
+    # call over all sources repeats one after the other.
     with tempfile.TemporaryDirectory(prefix="hip_ops_") as tmp:
-        objs = []
-        for s in NO_PACKED_FP32_SOURCES:
-            objs.append(str(Path(tmp) / (Path(s).stem + ".o")))
-            _run(common + NO_PACKED_FP32_FLAGS
-                 + ["-c", "-x", "hip", str(CSRC / s), "-o", objs[-1]],
-                 verbose)
-        # the objects go last: "-x none" ends the language override
-        _run(common + ["-shared", "-x", "hip"] + srcs + ["-x", "none"] + objs
+        jobs = [(s, []) for s in SOURCES] \
+            + [(s, NO_PACKED_FP32_FLAGS) for s in NO_PACKED_FP32_SOURCES]
+        objs = [str(Path(tmp) / (Path(s).stem + ".o")) for s, _ in jobs]
+        with ThreadPoolExecutor(min(COMPILE_JOBS, os.cpu_count() or 1)) as ex:
+            list(ex.map(
+                lambda job, obj: _run(
+                    common + job[1]
+                    + ["-c", "-x", "hip", str(CSRC / job[0]), "-o", obj],
+                    verbose),
+                jobs, objs))
+        _run(common + ["-shared"] + objs
              + [f"-L{torch_lib}", "-ltorch", "-ltorch_cpu", "-ltorch_hip",
                 "-lc10", "-lc10_hip", "-ltorch_python", "-lamdhip64",
                 f"-Wl,-rpath,{torch_lib}", "-o", str(OUT)], verbose)

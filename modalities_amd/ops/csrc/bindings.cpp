@@ -160,6 +160,13 @@ torch::Tensor skinny_linear(torch::Tensor x, torch::Tensor w,
                             c10::optional<torch::Tensor> scale,
                             c10::optional<torch::Tensor> bias);
 long skinny_linear_max_m();
+torch::Tensor skinny_linear_fused(torch::Tensor x, torch::Tensor w,
+                                  c10::optional<torch::Tensor> scale,
+                                  c10::optional<torch::Tensor> bias,
+                                  c10::optional<torch::Tensor> norm_weight,
+                                  double eps,
+                                  c10::optional<torch::Tensor> residual,
+                                  bool glu);
 torch::Tensor skinny_linear_mfma(torch::Tensor x, torch::Tensor w,
                                  c10::optional<torch::Tensor> scale,
                                  c10::optional<torch::Tensor> bias,
@@ -388,6 +395,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("bias") = py::none());
   m.def("skinny_linear_max_m", &skinny_linear_max_m,
         "largest batch (rows of x) skinny_linear takes");
+  m.def("skinny_linear_fused", &skinny_linear_fused,
+        "skinny_linear with an RMSNorm prologue (norm_weight bf16 [K], eps: x "
+        "is the raw input), a SwiGLU epilogue (glu: w is [2H,K] gate | up, y "
+        "is [M,H]) and a residual epilogue (residual bf16 [M,N_out]), each "
+        "optional; order: * inv_rms[m], * scale[n], + bias[n], gate, "
+        "+ residual, one rounding",
+        py::arg("x"), py::arg("w"), py::arg("scale") = py::none(),
+        py::arg("bias") = py::none(), py::arg("norm_weight") = py::none(),
+        py::arg("eps") = 1e-6, py::arg("residual") = py::none(),
+        py::arg("glu") = false);
   m.def("skinny_linear_mfma", &skinny_linear_mfma,
         "skinny_linear's contract for 1 <= M <= 32, on the matrix cores; "
         "rt / ksplit pick a tiling for A/B (0: the shipped one)",

@@ -64,6 +64,8 @@ import torch
 import torch.nn.functional as F
 
 from modalities_amd.ops.backend import hip_ext, use_hip
+from modalities_amd.ops.rms_norm import RMSNorm
+from modalities_amd.ops.swiglu import silu_mul_joint
 
 E4M3_MAX = 448.0
 SKINNY_MAX_M = 8
@@ -353,22 +355,113 @@ def _skinny_linear_ref(x, w, scale, bias):
     return acc.to(torch.bfloat16)
 
 
+def _check_fused_args(x, w, norm_weight, norm_eps, residual, glu):
+    M, K = x.shape
+    N = w.shape[0]
+    if norm_weight is not None:
+        if not isinstance(norm_weight, torch.Tensor) \
+                or norm_weight.dtype != torch.bfloat16:
+            raise TypeError("skinny_linear: norm_weight must be a bf16 tensor "
+                            "or None")
+        if tuple(norm_weight.shape) != (K,) or not norm_weight.is_contiguous():
+            raise ValueError(f"skinny_linear: norm_weight must be contiguous "
+                             f"[K] = {(K,)}, got {tuple(norm_weight.shape)}")
+        if norm_weight.device != x.device:
+            raise ValueError(f"skinny_linear: norm_weight is on "
+                             f"{norm_weight.device}, x on {x.device}")
+        if not norm_eps >= 0:
+            raise ValueError(f"skinny_linear: norm_eps must be >= 0, got "
+                             f"{norm_eps}")
+    if glu and N % 2 != 0:
+        raise ValueError(f"skinny_linear: glu needs an even N (gate | up "
+                         f"rows), got {N}")
+    if residual is not None:
+        n_out = N // 2 if glu else N
+        if not isinstance(residual, torch.Tensor) \
+                or residual.dtype != torch.bfloat16:
+            raise TypeError("skinny_linear: residual must be a bf16 tensor or "
+                            "None")
+        if tuple(residual.shape) != (M, n_out):
+            raise ValueError(f"skinny_linear: residual must be [M, N_out] = "
+                             f"{(M, n_out)}, got {tuple(residual.shape)}")
+        if residual.stride(1) != 1:
+            raise ValueError("skinny_linear: residual must have unit stride "
+                             "in N")
+        if residual.device != x.device:
+            raise ValueError(f"skinny_linear: residual is on "
+                             f"{residual.device}, x on {x.device}")
+
+
+def _skinny_linear_fused_ref(x, w, scale, bias, norm_weight, norm_eps,
+                             residual, glu):
+    xf = x.float()
+    if norm_weight is not None:
+        inv = torch.rsqrt(xf.pow(2).mean(-1, keepdim=True) + norm_eps)
+        xf = xf * norm_weight.float()
+    acc = xf @ w.float().t()
+    if norm_weight is not None:
+        acc = acc * inv
+    if scale is not None:
+        acc = acc * scale
+    if bias is not None:
+        acc = acc + bias.float()
+    if glu:
+        h = acc.shape[1] // 2
+        acc = F.silu(acc[:, :h]) * acc[:, h:]
+    if residual is not None:
+        acc = acc + residual.float()
+    return acc.to(torch.bfloat16)
+
+
 def skinny_linear(x: torch.Tensor, w: torch.Tensor,
                   scale: Optional[torch.Tensor] = None,
-                  bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+                  bias: Optional[torch.Tensor] = None, *,
+                  norm_weight: Optional[torch.Tensor] = None,
+                  norm_eps: float = 1e-6,
+                  residual: Optional[torch.Tensor] = None,
+                  glu: bool = False) -> torch.Tensor:
     """y [M, N] bf16 = x [M, K] . w [N, K]^T (* scale[n]) (+ bias[n]).
 
     x: bf16, 1 <= M <= 8, unit stride in K; rows may be strided (a view into
     a wider buffer). w: contiguous [N, K], float8_e4m3fn with `scale` fp32
     [N], or bf16 with scale None. bias: bf16 [N] or None. K % 16 == 0.
     A row's result does not depend on M or on where the row sits in x.
-    Inference only (no autograd)."""
+    Inference only (no autograd).
+
+    Three independent options fold the elementwise neighbours of a decode
+    GEMM into it (csrc/decode_gemv_fused.hip); with none set the call is the
+    plain kernel's, bit for bit:
+
+    * norm_weight bf16 [K], norm_eps: x is the raw input of an RMSNorm with
+      this weight; y is the linear of the normalised x, which is never
+      written: inv[m] * sum_k (x[m, k] g[k]) w[n, k] with inv[m] =
+      rsqrt(mean_k x[m, k]^2 + eps) applied once per output.
+    * glu: w is a packed [2H, K] gate | up weight (gate rows first, as
+      `SwiGLU.Wv` stores it) and y [M, H] = silu(gate) * up, each half after
+      its own scale and bias.
+    * residual bf16 [M, N_out] (unit stride in N): added last.
+
+    Order: * inv[m], * scale[n], + bias[n], gate, + residual, all in fp32,
+    then the one rounding to bf16. y is a fresh tensor."""
     _check_skinny_args(x, w, scale, bias)
-    if use_hip(x, w, scale, bias):
+    if norm_weight is None and residual is None and not glu:
+        if use_hip(x, w, scale, bias):
+            if (x.shape[0] > 1 and x.stride(0) % 8 != 0) \
+                    or x.data_ptr() % 16 != 0:
+                x = x.contiguous()   # the kernel reads x in 16-byte pieces
+            return hip_ext().skinny_linear(x, w, scale, bias)
+        return _skinny_linear_ref(x, w, scale, bias)
+    _check_fused_args(x, w, norm_weight, norm_eps, residual, glu)
+    if use_hip(x, w, scale, bias, norm_weight, residual):
         if (x.shape[0] > 1 and x.stride(0) % 8 != 0) or x.data_ptr() % 16 != 0:
             x = x.contiguous()   # the kernel reads x in 16-byte pieces
-        return hip_ext().skinny_linear(x, w, scale, bias)
-    return _skinny_linear_ref(x, w, scale, bias)
+        if norm_weight is not None and norm_weight.data_ptr() % 16 != 0:
+            norm_weight = norm_weight.clone()   # and g likewise
+        return hip_ext().skinny_linear_fused(x, w, scale, bias, norm_weight,
+                                             float(norm_eps), residual,
+                                             bool(glu))
+    return _skinny_linear_fused_ref(x, w, scale, bias, norm_weight, norm_eps,
+                                    residual, glu)
 
 
 def skinny_linear_mfma(x: torch.Tensor, w: torch.Tensor,
@@ -415,6 +508,31 @@ def set_decode_mfma_min_rows(n: int) -> None:
 
 def decode_mfma_min_rows() -> int:
     return _MFMA_MIN_ROWS
+
+
+_FUSED_STEP = os.environ.get("MA_DECODE_FUSED_STEP", "0")
+if _FUSED_STEP not in ("0", "1"):
+    raise ValueError(f"MA_DECODE_FUSED_STEP must be 0 or 1, got "
+                     f"{_FUSED_STEP!r}")
+_FUSED_STEP = _FUSED_STEP == "1"
+
+
+def set_decode_fused_step(on: bool) -> None:
+    """Whether a single-token step on prepared bf16 / e4m3 decode weights
+    folds its RMSNorms, its SwiGLU gate and its residual adds into the skinny
+    GEMMs next to them (`skinny_linear`'s norm_weight / glu / residual):
+    5 of about 13 launches per layer. Off by default; MA_DECODE_FUSED_STEP
+    sets the initial value. The fused step agrees with the unfused one to
+    rounding, not bit for bit: it skips the bf16 roundings in between."""
+    global _FUSED_STEP
+    if not isinstance(on, bool):
+        raise ValueError(f"set_decode_fused_step: on must be a bool, got "
+                         f"{on!r}")
+    _FUSED_STEP = on
+
+
+def decode_fused_step() -> bool:
+    return _FUSED_STEP
 
 
 class PreparedLinear(NamedTuple):
@@ -466,7 +584,57 @@ def get_prepared(lin: torch.nn.Module) -> Optional[PreparedLinear]:
     return lin.__dict__.get(_ATTR)
 
 
-def step_linear(lin: torch.nn.Module, x: torch.Tensor) -> torch.Tensor:
+def _fused_step_ok(prep, x, rows, norm, residual) -> bool:
+    if not _FUSED_STEP or prep is None or prep.w.dtype == torch.uint8:
+        return False
+    if not 1 <= rows <= SKINNY_MAX_M or (x.is_cuda and rows >= _MFMA_MIN_ROWS):
+        return False
+    if x.dtype != torch.bfloat16 or x.device != prep.w.device:
+        return False
+    if norm is not None and not (
+            isinstance(norm, RMSNorm) and norm.weight.dtype == torch.bfloat16
+            and tuple(norm.weight.shape) == (x.shape[-1],)
+            and norm.weight.device == x.device):
+        return False
+    return residual is None or (residual.dtype == torch.bfloat16
+                                and residual.device == x.device)
+
+
+def step_linear(lin: torch.nn.Module, x: torch.Tensor,
+                norm: Optional[torch.nn.Module] = None,
+                residual: Optional[torch.Tensor] = None,
+                glu: bool = False) -> torch.Tensor:
+    """`lin(x)` for a single-token step, optionally with its neighbours:
+    residual + gate(lin(norm(x))), where `norm` is the norm module in front
+    of `lin`, glu=True gates a packed gate | up projection (`silu_mul_joint`)
+    and `residual` is added last. With `set_decode_fused_step(True)`, a
+    prepared bf16 / e4m3 copy, at most 8 rows on the VALU route and `norm`
+    (if given) an `ops.rms_norm.RMSNorm` over K, the whole expression is one
+    `skinny_linear` launch with the fused options. In every other case (the
+    switch off, an MXFP4 copy, a batch on the MFMA route, a LayerNorm, a
+    layer without a prepared copy) it is the composition of the pieces as
+    they run unfused, bit for bit: `norm(x)`, the linear below,
+    `silu_mul_joint`, the add."""
+    if norm is None and residual is None and not glu:
+        return _step_linear(lin, x)
+    prep = lin.__dict__.get(_ATTR)
+    rows = x.numel() // x.shape[-1]
+    if _fused_step_ok(prep, x, rows, norm, residual):
+        n_out = prep.w.shape[0] // 2 if glu else prep.w.shape[0]
+        y = skinny_linear(
+            x.reshape(rows, x.shape[-1]), prep.w, prep.scale, prep.bias,
+            norm_weight=None if norm is None else norm.weight.detach(),
+            norm_eps=1e-6 if norm is None else norm.eps,
+            residual=None if residual is None
+            else residual.reshape(rows, n_out), glu=glu)
+        return y.view(*x.shape[:-1], n_out)
+    y = _step_linear(lin, x if norm is None else norm(x))
+    if glu:
+        y = silu_mul_joint(y)
+    return y if residual is None else residual + y
+
+
+def _step_linear(lin: torch.nn.Module, x: torch.Tensor) -> torch.Tensor:
     """`lin(x)` for a single-token step x [B, 1, K]: on the prepared weight
     when `lin` has one, B <= 32 and x is bf16 on the weight's device --
     through `skinny_linear` for B <= 8, through `skinny_linear_mfma` for

@@ -139,7 +139,14 @@ def main():
                          "bf16 KV cache over 64 greedy tokens")
     ap.add_argument("--no-reforward", action="store_true",
                     help="skip the full-context re-forward comparison")
+    ap.add_argument("--fused", action="store_true",
+                    help="turn the fused decode step on "
+                         "(ops.set_decode_fused_step): norms, SwiGLU gate and "
+                         "residual adds ride on the bf16 / fp8_e4m3 GEMMs")
     args = ap.parse_args()
+    if args.fused:
+        from modalities_amd.ops import set_decode_fused_step
+        set_decode_fused_step(True)
     model, cfg = build_model()
     for weights in args.weights:
         model.clear_decode_weights()
@@ -171,7 +178,8 @@ def run(model, cfg, args):
                 if args.no_reforward:
                     print(f"ctx {ctx}: cached {cached_ms:.2f} ms/tok  "
                           f"[batch {batch}, {args.impl}, "
-                          f"weights {args.weights}, kv {args.kv_format}]")
+                          f"weights {args.weights}, kv {args.kv_format}"
+                          f"{', fused' if args.fused else ''}]")
                     continue
 
                 full = ids

@@ -16,6 +16,12 @@ the MFMA kernel's RT x KSPLIT instantiations on the e4m3 weight instead (the
 A/B behind the shipped MFMA_GEMV_RT / MFMA_GEMV_KSPLIT) and the MXFP4
 kernel's RT = 1, 2, 4 (the A/B behind SKINNY_FP4_FILL_WGS).
 
+`--fused` times, for M <= 8 on the bf16 and e4m3 weights, each decode GEMM
+with its elementwise neighbours as separate launches against the one fused
+launch (`skinny_linear`'s norm_weight / glu / residual): rms_norm + GEMM for
+QKV and lm_head, rms_norm + GEMM + silu_mul_joint for W|V, GEMM + add for
+c_proj and W_2.
+
 A decode step streams every weight of the model once per token, so each
 weight arrives cold. To time that and not a cache-resident loop, every shape
 gets enough copies of its weight that one format's set exceeds `--cold-mb`
@@ -28,7 +34,7 @@ gives the median and the min..max spread. GB/s counts the weight bytes only.
 
     PYTHONPATH=. python tools/decode_gemv_bench.py [--m 1 8 16 32]
         [--repeats 7] [--calls 64] [--cold-mb 768] [--tilings]
-        [--only qkv c_proj wv w2 lm_head]
+        [--only qkv c_proj wv w2 lm_head] [--fused]
 """
 
 import argparse
@@ -76,6 +82,67 @@ def replay_us(g, ncalls):
     return t0.elapsed_time(t1) / ncalls * 1e3
 
 
+def fused_ab(args):
+    """The unfused launch sequence of each decode GEMM against the fused
+    launch, same cold-weight graph timing as the main table."""
+    from modalities_amd.ops import (quantize_weight_fp8, rms_norm,
+                                    silu_mul_joint, skinny_linear)
+    from modalities_amd.ops.decode_linear import SKINNY_MAX_M
+    for name, (N, K) in shapes_2p7b().items():
+        if args.only and name not in args.only:
+            continue
+        w = (torch.randn(N, K, device="cuda") * 0.02).bfloat16()
+        wq, scale = quantize_weight_fp8(w)
+        ncopy = max(2, -(-args.cold_mb * (1 << 20) // (N * K)))
+        ncalls = max(args.calls, ncopy)
+        sets = {"bf16": ([w.clone() for _ in range(ncopy)], None),
+                "e4m3": ([wq.clone() for _ in range(ncopy)], scale)}
+        g = (1 + 0.1 * torch.randn(K, device="cuda")).bfloat16()
+        glu = name == "wv"
+        for M in (m for m in args.m if m <= SKINNY_MAX_M):
+            x = torch.randn(M, K, device="cuda").bfloat16()
+            r = torch.randn(M, N, device="cuda").bfloat16()
+            impls = {}
+            for fmt, (ws, sc) in sets.items():
+                if name in ("c_proj", "w2"):
+                    impls[fmt] = lambda i, ws=ws, sc=sc: \
+                        r + skinny_linear(x, ws[i % ncopy], sc)
+                    impls[fmt + "-fused"] = lambda i, ws=ws, sc=sc: \
+                        skinny_linear(x, ws[i % ncopy], sc, residual=r)
+                elif glu:
+                    impls[fmt] = lambda i, ws=ws, sc=sc: silu_mul_joint(
+                        skinny_linear(rms_norm(x, g), ws[i % ncopy], sc))
+                    impls[fmt + "-fused"] = lambda i, ws=ws, sc=sc: \
+                        skinny_linear(x, ws[i % ncopy], sc, norm_weight=g,
+                                      glu=True)
+                else:
+                    impls[fmt] = lambda i, ws=ws, sc=sc: skinny_linear(
+                        rms_norm(x, g), ws[i % ncopy], sc)
+                    impls[fmt + "-fused"] = lambda i, ws=ws, sc=sc: \
+                        skinny_linear(x, ws[i % ncopy], sc, norm_weight=g)
+            graphs = {k: capture(fn, ncalls) for k, fn in impls.items()}
+            for gr, _ in graphs.values():
+                replay_us(gr, ncalls)
+            us = {k: [] for k in impls}
+            for _ in range(args.repeats):
+                for k, (gr, _) in graphs.items():
+                    us[k].append(replay_us(gr, ncalls))
+            line = f"{name:8s} N{N:6d} K{K:5d} M{M}:"
+            med = {k: statistics.median(v) for k, v in us.items()}
+            for k in impls:
+                line += (f"  {k} {med[k]:7.2f} us [{min(us[k]):.2f}.."
+                         f"{max(us[k]):.2f}]")
+            line += "  |" + "".join(
+                f" {f}/fused {med[f] / med[f + '-fused']:.2f}x" for f in sets)
+            line += "  | maxdiff" + "".join(
+                f" {f} {(graphs[f][1][0].float() - graphs[f + '-fused'][1][0].float()).abs().max().item():.1e}"
+                for f in sets)
+            print(line, flush=True)
+            del graphs
+        del sets
+        torch.cuda.empty_cache()
+
+
 def main():
     from modalities_amd.ops import (dequantize_weight_mxfp4,
                                     quantize_weight_fp8, quantize_weight_mxfp4,
@@ -96,10 +163,15 @@ def main():
     ap.add_argument("--tilings", action="store_true",
                     help="time skinny_linear_mfma's RT x KSPLIT variants on "
                          "the e4m3 weight instead of the implementations")
+    ap.add_argument("--fused", action="store_true",
+                    help="time each GEMM plus its norm / gate / add launches "
+                         "against the fused launch (M <= 8, bf16 and e4m3)")
     args = ap.parse_args()
     torch.manual_seed(0)
     print(f"# cold set >= {args.cold_mb} MB per format; time per call inside "
           f"a replayed graph; median [min..max] of {args.repeats} replays")
+    if args.fused:
+        return fused_ab(args)
     for name, (N, K) in shapes_2p7b().items():
         if args.only and name not in args.only:
             continue
