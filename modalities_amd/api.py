@@ -182,7 +182,8 @@ def _build_text_inference_component(config_path: Path):
         use_decode_graph=gen_cfg.get("use_decode_graph", True),
         device_sampling=gen_cfg.get("device_sampling", False),
         decode_weight_format=gen_cfg.get("decode_weight_format"),
-        kv_cache_format=gen_cfg.get("kv_cache_format"))
+        kv_cache_format=gen_cfg.get("kv_cache_format"),
+        prefill_chunk_tokens=gen_cfg.get("prefill_chunk_tokens"))
     return comp
 
 

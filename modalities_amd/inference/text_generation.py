@@ -26,6 +26,14 @@ has the model allocate an e4m3 KV cache (GPT2LLM.new_kv_cache(kv_format=...)):
 stores quantised. It pays where the cache, not the weights, is the traffic:
 large batch times long context (profiles/decode_attention.md).
 
+`prefill_chunk_tokens` (an integer >= 2; default None = the prompt in one
+piece) feeds a longer prompt to `forward_cached` in chunks of that many
+tokens: the first chunk takes the prefill kernel, the later ones attend over
+the cache in place through `ops.decode_attention` (for the duration of the
+prefill `ops.decode_chunk_tokens()` is raised to at least the chunk size),
+which bounds the activation memory of a long prompt. With an FP8 cache a
+chunk reads its own rows quantised.
+
 `device_sampling=True` (default off) samples with `ops.sample_logits`: one
 HIP kernel for temperature, top-k, top-p and the draw, reading the logits
 where lm_head left them. A captured decode step then ends in `torch.rand`
@@ -142,7 +150,8 @@ class TextInferenceComponent:
                  use_decode_graph: bool = True,
                  decode_weight_format: Optional[str] = None,
                  kv_cache_format: Optional[str] = None,
-                 device_sampling: bool = False):
+                 device_sampling: bool = False,
+                 prefill_chunk_tokens: Optional[int] = None):
         if decode_weight_format is not None \
                 and not hasattr(model, "prepare_decode_weights"):
             raise ValueError(
@@ -158,6 +167,12 @@ class TextInferenceComponent:
                 raise ValueError(
                     f"kv_cache_format={kv_cache_format!r}: "
                     f"{type(model).__name__} has no KV cache")
+        if prefill_chunk_tokens is not None and (
+                not isinstance(prefill_chunk_tokens, int)
+                or isinstance(prefill_chunk_tokens, bool)
+                or prefill_chunk_tokens < 2):
+            raise ValueError(f"prefill_chunk_tokens must be None or an "
+                             f"integer >= 2, got {prefill_chunk_tokens!r}")
         self.model = model
         self.tokenizer = tokenizer
         self.prompt_template = prompt_template
@@ -173,6 +188,27 @@ class TextInferenceComponent:
         self.decode_weight_format = decode_weight_format
         self.kv_cache_format = kv_cache_format
         self.device_sampling = device_sampling
+        self.prefill_chunk_tokens = prefill_chunk_tokens
+
+    def _prefill(self, input_ids: torch.Tensor, cache) -> dict:
+        """The prompt into the cache: in one piece, or in chunks of
+        prefill_chunk_tokens with the multi-token decode route open to
+        them. Returns the output of the last piece."""
+        n = self.prefill_chunk_tokens
+        if n is None or input_ids.shape[1] <= n:
+            return self.model.forward_cached({self.sample_key: input_ids},
+                                             cache)
+        from modalities_amd.ops.attention import (decode_chunk_tokens,
+                                                  set_decode_chunk_tokens)
+        was = decode_chunk_tokens()
+        set_decode_chunk_tokens(max(was, n))
+        try:
+            for p in range(0, input_ids.shape[1], n):
+                out = self.model.forward_cached(
+                    {self.sample_key: input_ids[:, p:p + n]}, cache)
+        finally:
+            set_decode_chunk_tokens(was)
+        return out
 
     def _sampler(self) -> tuple:
         """(temperature, top_k, top_p) as ops.sample_logits takes them."""
@@ -238,7 +274,7 @@ class TextInferenceComponent:
             cache = self.model.new_kv_cache(input_ids.shape[0],
                                             max_len=self.sequence_length,
                                             **kw)
-            out = self.model.forward_cached({self.sample_key: input_ids}, cache)
+            out = self._prefill(input_ids, cache)
         else:
             out = self.model({self.sample_key: input_ids})
 

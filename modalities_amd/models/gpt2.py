@@ -251,8 +251,9 @@ class CausalSelfAttention(nn.Module):
         A multi-token step with dec given (GPT2LLM.forward_cached gives it
         for 2 <= T <= `decode_chunk_tokens()` at pos > 0; lens_dev then
         holds pos + T) stores its K/V as above and attends through
-        `decode_attention`, which reads the cache in place: no copy of the
-        prefix, no de-quantised prefix, no cat. With an FP8 cache the
+        `decode_attention`, which reads the cache in place (the chunk or,
+        for long chunks, the wide kernel): no copy of the prefix, no
+        de-quantised prefix, no cat. With an FP8 cache the
         chunk's own rows are then read from the cache, hence quantised, as
         a single-token step reads its own row; the route above attends on
         the chunk's fresh bf16 rows.
@@ -586,7 +587,9 @@ class GPT2LLM(NNModel):
         conditions a step of 2 <= T <= `ops.decode_chunk_tokens()` tokens
         at pos > 0 attends through the multi-token decode kernels
         (`set_decode_chunk_tokens` / MA_DECODE_CHUNK_TOKENS; 0, the
-        default, sends none there)."""
+        default, sends none there): attention_decode_chunk.hip below 128
+        query rows per kv head (T * Hq / Hkv), attention_decode_wide.hip
+        from there up, e.g. the chunks of a chunked prefill."""
         input_ids = inputs[self.sample_key]
         B, T = input_ids.shape
         pos = cache.pos

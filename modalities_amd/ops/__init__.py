@@ -13,7 +13,10 @@ torch SDPA/LayerNorm/CE/AdamW) with hand-written gfx950 HIP kernels:
                           k_scale / v_scale on the two decode ops): D + 4
                           bytes per cached row instead of 2 D; MFMA split-KV
                           attention of a few new tokens per row over either
-                          cache format (decode_attention with T >= 2)
+                          cache format (decode_attention with T >= 2), and
+                          from 128 query rows per kv head a variant that
+                          stages the keys through LDS once per 64 rows
+                          (long chunks: chunked prefill, multi-turn chat)
 - K3  skinny_linear     : M <= 8 decode GEMM streaming bf16 or weight-only
                           e4m3 weights straight to registers; optionally with
                           an RMSNorm prologue, a SwiGLU gate and a residual

@@ -47,9 +47,19 @@ a bf16 cache of de-quantised values is an exact reference for the FP8 route
 Multi-token steps (csrc/attention_decode_chunk.hip): `decode_attention` with
 T >= 2 query tokens per row (a speculative-decoding verify step, the next
 turn of a cached chat, a chunk of a chunked prefill) runs an MFMA split-KV
-kernel that reads either cache format in place, once for all T * (Hq / Hkv)
-query rows of a kv head. `set_decode_chunk_tokens` / MA_DECODE_CHUNK_TOKENS
-is the largest T the model sends there (0, the default: none)."""
+kernel that reads either cache format in place, once per tile of 16 of the
+T * (Hq / Hkv) query rows of a kv head. `set_decode_chunk_tokens` /
+MA_DECODE_CHUNK_TOKENS is the largest T the model sends there (0, the
+default: none).
+
+Long token chunks (csrc/attention_decode_wide.hip): from
+`_DECODE_WIDE_MIN_ROWS` query rows per kv head up (MA_DECODE_WIDE_MIN_ROWS
+sets the initial value), `decode_attention` runs a second MFMA split-KV
+kernel in which a workgroup of 4 waves stages the keys through LDS once for
+64 query rows, each wave keeping a 16-row tile and its softmax state in
+registers: a chunk of a chunked prefill, the next turn of a cached chat, a
+long verify step. Same contract, both cache formats, read in place; below
+the border nothing changes."""
 
 import math
 import os
@@ -450,7 +460,10 @@ def set_decode_chunk_tokens(n: int) -> None:
     `GPT2LLM.forward_cached` at pos > 0 attends through the multi-token
     decode kernels (`decode_attention` with T >= 2) instead of the prefill
     kernel on a copy of the prefix. 0 (the default) sends none there.
-    MA_DECODE_CHUNK_TOKENS sets the initial value."""
+    MA_DECODE_CHUNK_TOKENS sets the initial value. Of those steps the ones
+    with fewer than `_DECODE_WIDE_MIN_ROWS` query rows per kv head
+    (T * Hq / Hkv) run csrc/attention_decode_chunk.hip, the others
+    csrc/attention_decode_wide.hip."""
     global _DECODE_CHUNK_TOKENS
     if not isinstance(n, int) or isinstance(n, bool) or n < 0:
         raise ValueError(f"set_decode_chunk_tokens: n must be an integer "
@@ -460,6 +473,15 @@ def set_decode_chunk_tokens(n: int) -> None:
 
 def decode_chunk_tokens() -> int:
     return _DECODE_CHUNK_TOKENS
+
+
+# Query rows per kv head, T * (Hq / Hkv), from which a multi-token step takes
+# the wide kernel (64 rows per workgroup) instead of the chunk kernel (16).
+# 128 is the measured crossing (profiles/decode_attention.md, "Long token
+# chunks"): the smallest measured row count from which the wide kernel beats
+# the chunk kernel at every measured shape; at 64 rows it still loses at
+# batch 1, short context, where its few workgroups leave the chip idle.
+_DECODE_WIDE_MIN_ROWS = int(os.environ.get("MA_DECODE_WIDE_MIN_ROWS", "128"))
 
 
 def _check_index_arg(name, t, ref, B):
@@ -661,27 +683,30 @@ def decode_attention(q: torch.Tensor, k_cache: torch.Tensor,
     0 .. kv_lens[b]-1. A query that sees no row gives zeros, and nothing at
     or beyond the length is read. Returns o [B,T,Hq,D].
     D in {64, 80, 128}; inference only (no autograd). On the GPU T == 1
-    takes the split-KV decode kernels, T >= 2 the MFMA multi-token ones
-    (csrc/attention_decode_chunk.hip).
+    takes the split-KV decode kernels, T >= 2 the MFMA multi-token ones:
+    csrc/attention_decode_chunk.hip (a workgroup per 16 query rows) while
+    T * (Hq / Hkv) is below `_DECODE_WIDE_MIN_ROWS`, and
+    csrc/attention_decode_wide.hip (a workgroup per 64) from there up.
 
     FP8 cache: k_cache, v_cache hold float8_e4m3fn codes and k_scale,
     v_scale their fp32 [B,Lmax,Hkv] scales (`quantize_kv_fp8`); the result
     is attention over scale * code."""
     _check_decode_args(q, k_cache, v_cache, kv_lens)
-    multi = q.shape[1] > 1
+    T = q.shape[1]
+    route = "" if T == 1 else "_chunk" \
+        if T * (q.shape[2] // k_cache.shape[2]) < _DECODE_WIDE_MIN_ROWS \
+        else "_wide"
     if _check_cache_scales(k_cache, v_cache, k_scale, v_scale):
         if use_hip(q, k_cache, v_cache, kv_lens, k_scale, v_scale):
-            fwd = hip_ext().decode_attn_chunk_fp8_fwd if multi \
-                else hip_ext().decode_attn_fp8_fwd
+            fwd = getattr(hip_ext(), f"decode_attn{route}_fp8_fwd")
             o, _ = fwd(q, k_cache, k_scale, v_cache, v_scale, kv_lens)
             return o
         return _decode_attention_ref(
             q, _dequantize_prefix(k_cache, k_scale, kv_lens),
             _dequantize_prefix(v_cache, v_scale, kv_lens), kv_lens)
     if use_hip(q, k_cache, v_cache, kv_lens):
-        fwd = hip_ext().decode_attn_chunk_fwd if multi \
-            else hip_ext().decode_attn_fwd
-        o, _ = fwd(q, k_cache, v_cache, kv_lens)
+        o, _ = getattr(hip_ext(), f"decode_attn{route}_fwd")(
+            q, k_cache, v_cache, kv_lens)
         return o
     return _decode_attention_ref(q, k_cache, v_cache, kv_lens)
 

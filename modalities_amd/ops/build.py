@@ -31,6 +31,7 @@ SOURCES = [
     "attention_v2.hip",
     "attention_decode.hip",
     "attention_decode_chunk.hip",
+    "attention_decode_wide.hip",
     "decode_gemv.hip",
     "decode_gemv_fused.hip",
     "decode_gemv_mfma.hip",

@@ -156,6 +156,22 @@ std::vector<torch::Tensor> decode_attn_chunk_fp8_fwd(torch::Tensor q,
 long decode_attn_chunk_kv_chunk();
 long decode_attn_chunk_kv_chunk_min();
 long decode_attn_chunk_wave_keys();
+std::vector<torch::Tensor> decode_attn_wide_fwd(torch::Tensor q,
+                                                torch::Tensor k_cache,
+                                                torch::Tensor v_cache,
+                                                torch::Tensor kv_lens,
+                                                long kv_chunk);
+std::vector<torch::Tensor> decode_attn_wide_fp8_fwd(torch::Tensor q,
+                                                    torch::Tensor k_codes,
+                                                    torch::Tensor k_scale,
+                                                    torch::Tensor v_codes,
+                                                    torch::Tensor v_scale,
+                                                    torch::Tensor kv_lens,
+                                                    long kv_chunk);
+long decode_attn_wide_kv_chunk();
+long decode_attn_wide_kv_chunk_min();
+long decode_attn_wide_key_step();
+long decode_attn_wide_rows();
 torch::Tensor skinny_linear(torch::Tensor x, torch::Tensor w,
                             c10::optional<torch::Tensor> scale,
                             c10::optional<torch::Tensor> bias);
@@ -386,6 +402,26 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "smallest legal kv_chunk override of decode_attn_chunk_fwd");
   m.def("decode_attn_chunk_wave_keys", &decode_attn_chunk_wave_keys,
         "keys a wave of decode_attn_chunk_fwd consumes per step");
+  m.def("decode_attn_wide_fwd", &decode_attn_wide_fwd,
+        "decode_attn_chunk_fwd's contract for long token chunks: one "
+        "workgroup stages the keys through LDS for 64 query rows; returns "
+        "(o, lse [B,Hq,T])",
+        py::arg("q"), py::arg("k_cache"), py::arg("v_cache"),
+        py::arg("kv_lens"), py::arg("kv_chunk") = 0);
+  m.def("decode_attn_wide_fp8_fwd", &decode_attn_wide_fp8_fwd,
+        "decode_attn_wide_fwd over e4m3 code caches [B,Lmax,Hkv,D] with "
+        "fp32 scales [B,Lmax,Hkv]",
+        py::arg("q"), py::arg("k_codes"), py::arg("k_scale"),
+        py::arg("v_codes"), py::arg("v_scale"), py::arg("kv_lens"),
+        py::arg("kv_chunk") = 0);
+  m.def("decode_attn_wide_kv_chunk", &decode_attn_wide_kv_chunk,
+        "default keys per workgroup of decode_attn_wide_fwd");
+  m.def("decode_attn_wide_kv_chunk_min", &decode_attn_wide_kv_chunk_min,
+        "smallest legal kv_chunk override of decode_attn_wide_fwd");
+  m.def("decode_attn_wide_key_step", &decode_attn_wide_key_step,
+        "keys a workgroup of decode_attn_wide_fwd stages per step");
+  m.def("decode_attn_wide_rows", &decode_attn_wide_rows,
+        "query rows a workgroup of decode_attn_wide_fwd owns");
   // Skinny GEMM for single-token decoding (weight-only e4m3 or bf16).
   m.def("skinny_linear", &skinny_linear,
         "y [M,N] bf16 = x [M,K] bf16 . w [N,K]^T for 1 <= M <= 8, K % 16 == 0; "

@@ -2,14 +2,17 @@
 tokens per row, already stored, against a cache of `ctx` rows in all.
 
   chunk  decode_attn_chunk_fwd / decode_attn_chunk_fp8_fwd, cache read in
-         place (ops.decode_attention with T >= 2)
+         place (ops.decode_attention with T >= 2, few query rows)
+  wide   decode_attn_wide_fwd / decode_attn_wide_fp8_fwd, the same call
+         with one workgroup per 64 query rows (ops.decode_attention from
+         _DECODE_WIDE_MIN_ROWS rows per kv head up)
   flash  what forward_cached does with the switch off, for the same call:
          bf16  attn_fwd on cache[:, :ctx].contiguous(), both prefix copies
                included, q_offset = ctx - T
          fp8   dequantize_kv_fp8 of the ctx - T prefix rows, torch.cat of
                the T fresh bf16 rows, then the bf16 chain
 
-The two routes alternate inside one process (`--rounds` rounds of `--iters`
+The routes alternate inside one process (`--rounds` rounds of `--iters`
 calls each, device events around each batch of calls); the figure is the
 median round. The cache rate is the bytes the call must move, 2 * B * ctx *
 Hkv * D * 2 (bf16) or 2 * B * ctx * Hkv * (D + 4) (fp8), over the CALL time
@@ -19,7 +22,7 @@ For kernel times run it under `rocprofv3 --kernel-trace --stats` with
 
     PYTHONPATH=. python tools/decode_chunk_bench.py [--ctx 2048 16384]
         [--batch 1 8] [--shape 32:32:80 32:8:128] [--tokens 2 4 8 16 32 64]
-        [--kv-format bf16 fp8_e4m3] [--kv-chunk 0]
+        [--kv-format bf16 fp8_e4m3] [--kv-chunk 0] [--wide-chunk 0]
 """
 
 import argparse
@@ -65,13 +68,16 @@ def main():
                     choices=["bf16", "fp8_e4m3"])
     ap.add_argument("--kv-chunk", type=int, default=0,
                     help="0 = the compiled default")
+    ap.add_argument("--wide-chunk", type=int, default=0,
+                    help="kv_chunk of the wide entries, 0 = their default")
     ap.add_argument("--no-flash", action="store_true",
                     help="skip the baseline route")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--iters", type=int, default=20)
     args = ap.parse_args()
-    ch = args.kv_chunk
-    print(f"default kv_chunk {ext.decode_attn_chunk_kv_chunk()}")
+    ch, wch = args.kv_chunk, args.wide_chunk
+    print(f"default kv_chunk {ext.decode_attn_chunk_kv_chunk()}, wide "
+          f"{ext.decode_attn_wide_kv_chunk()}")
     for shape in args.shape:
         Hq, Hkv, D = (int(x) for x in shape.split(":"))
         for B in args.batch:
@@ -92,6 +98,10 @@ def main():
                                 return ext.decode_attn_chunk_fwd(
                                     q, kc, vc, lens, ch)[0]
 
+                            def wide():
+                                return ext.decode_attn_wide_fwd(
+                                    q, kc, vc, lens, wch)[0]
+
                             def flash():
                                 return ext.attn_fwd(
                                     q, kc[:, :n].contiguous(),
@@ -104,6 +114,10 @@ def main():
                                 return ext.decode_attn_chunk_fp8_fwd(
                                     q, kq, ks, vq, vs, lens, ch)[0]
 
+                            def wide():
+                                return ext.decode_attn_wide_fp8_fwd(
+                                    q, kq, ks, vq, vs, lens, wch)[0]
+
                             def flash():
                                 p = n - T
                                 k = torch.cat([dequantize_kv_fp8(
@@ -114,16 +128,21 @@ def main():
                                                     v.contiguous(), True, p)[0]
                         line = f"{fmt} Hq{Hq} Hkv{Hkv} D{D} B{B} ctx{n} T{T}:"
                         if args.no_flash:
-                            us_c, = alternate([chunk], args.rounds, args.iters)
-                        else:
-                            us_c, us_f = alternate([chunk, flash], args.rounds,
+                            us_c, us_w = alternate([chunk, wide], args.rounds,
                                                    args.iters)
+                        else:
+                            us_c, us_w, us_f = alternate(
+                                [chunk, wide, flash], args.rounds, args.iters)
                             err = (chunk().float() - flash().float()
                                    ).abs().max().item()
                             line += (f" flash {us_f:8.1f} us | speed-up "
                                      f"{us_f / us_c:5.2f}x maxdiff {err:.1e} |")
+                        werr = (chunk().float() - wide().float()
+                                ).abs().max().item()
                         line += (f" chunk {us_c:7.1f} us "
-                                 f"{nbytes / us_c / 1e6:6.3f} TB/s")
+                                 f"{nbytes / us_c / 1e6:6.3f} TB/s | wide "
+                                 f"{us_w:7.1f} us {nbytes / us_w / 1e6:6.3f} "
+                                 f"TB/s vs chunk {werr:.1e}")
                         print(line, flush=True)
 
 
