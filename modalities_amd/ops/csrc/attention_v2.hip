@@ -13,8 +13,13 @@
 //     LDS buffer in all three kernels (HBM latency hides under MFMAs).
 //   - ds_read_b64_tr_b16 batches of 8 with a single lgkmcnt drain per
 //     d-block (v1 fwd drained per MFMA pair).
-//   - heavy-first block order for the causal triangle (fwd/dq blocks with
-//     the most kv tiles dispatch first).
+//   - globally heavy-first workgroup order for the causal triangle: a 1-D
+//     grid of n_blk*H*B ids, id = rank*(H*B) + b*H + h, rank 0 the block
+//     with the most tiles (see wg_decode). Every (b, h) dispatches its
+//     heaviest block before any dispatches its second heaviest, and any 8
+//     consecutive ids (one per XCD under round-robin dispatch) cost the
+//     same. MA_ATTN_GRID=legacy restores the dim3(n_blk, H, B) grid, which
+//     is heavy-first only inside one head (A/B).
 //   - per-wave fully-masked-tile skip (waves outside the causal band for
 //     a tile skip its MFMAs but keep the barrier schedule).
 //   - head_dim 80 (the reference 2.7B shape, gpt2_model.py:446-461)
@@ -37,6 +42,8 @@
 #include <c10/hip/HIPCachingAllocator.h>
 #include <c10/hip/HIPStream.h>
 
+#include <cstring>
+
 #include "attn_common.h"
 
 namespace attn2 {
@@ -51,6 +58,28 @@ constexpr int KVBLK = 64;   // fwd/dq kv tile rows
 constexpr int QBLK = 32;    // q rows per wave (fwd/dq) / per LDS tile (dkdv)
 constexpr int NW = 8;       // waves per workgroup
 constexpr int NT = NW * 64; // threads per workgroup
+
+// Workgroup -> (block, head, batch). `rank` orders the blocks of one (b, h)
+// by causal cost, 0 = most tiles: fwd/dq blocks count down from the last q
+// block (REVERSE), dkdv blocks count up from kv block 0. Linear grid:
+// blockIdx.x = rank*(H*B) + b*H + h; legacy grid: dim3(n_blk, H, B) with
+// rank = blockIdx.x. All values are workgroup-uniform.
+struct WgId { int blk, h, b; };
+template <bool REVERSE>
+static __device__ __forceinline__ WgId wg_decode(int n_blk, int H, int B,
+                                                 int legacy) {
+  int rank, h, b;
+  if (legacy) {
+    rank = blockIdx.x; h = blockIdx.y; b = blockIdx.z;
+  } else {
+    const unsigned hb = (unsigned)H * (unsigned)B;
+    const unsigned bh = blockIdx.x % hb;
+    rank = (int)(blockIdx.x / hb);
+    h = (int)(bh % (unsigned)H);
+    b = (int)(bh / (unsigned)H);
+  }
+  return {REVERSE ? n_blk - 1 - rank : rank, h, b};
+}
 
 template <int D> struct Geom {
   static constexpr int DS = (D == 64) ? 64 : 128;  // logical column count
@@ -143,15 +172,16 @@ struct FwdV2 {
                              float* __restrict__ lse, int B, int Tq, int Tkv,
                              int q_off, int Hq, int Hkv, float scale,
                              const int* __restrict__ doc_start,
-                             char* smem_raw) {
+                             int n_blk, int grid_legacy, char* smem_raw) {
     const int lane = threadIdx.x & 63;
     const int wid = threadIdx.x >> 6;
     const int hi = lane >> 5, ln31 = lane & 31;
 
     // heavy-first: high q blocks have the most kv tiles under causal
-    const int qi = (int)gridDim.x - 1 - (int)blockIdx.x;
+    const WgId wg = wg_decode<true>(n_blk, Hq, B, grid_legacy);
+    const int qi = wg.blk;
     const int qblk0 = qi * WG_Q;
-    const int h = blockIdx.y, b = blockIdx.z;
+    const int h = wg.h, b = wg.b;
     const int hkv = h / (Hq / Hkv);
 
     const long q_base = (((long)b * Tq) * Hq + h) * D;
@@ -492,13 +522,14 @@ struct DQV2 {
                              unsigned short* dq, int B, int Tq, int Tkv,
                              int q_off, int Hq, int Hkv, float scale,
                              const int* __restrict__ doc_start,
-                             char* smem_raw) {
+                             int n_blk, int grid_legacy, char* smem_raw) {
     const int lane = threadIdx.x & 63;
     const int wid = threadIdx.x >> 6;
     const int hi = lane >> 5, ln31 = lane & 31;
-    const int h = blockIdx.y, b = blockIdx.z;
+    const WgId wg = wg_decode<true>(n_blk, Hq, B, grid_legacy);
+    const int h = wg.h, b = wg.b;
     const int hkv = h / (Hq / Hkv);
-    const int qi = (int)gridDim.x - 1 - (int)blockIdx.x;  // heavy-first
+    const int qi = wg.blk;  // heavy-first
     const int qblk0 = qi * WG_Q;
     const int qg = qblk0 + wid * QBLK + ln31;  // LOCAL q row
     const int qgl = qg + q_off;
@@ -832,16 +863,18 @@ struct DKDVV2 {
                              int B, int Tq, int Tkv, int q_off, int Hq,
                              int Hkv, float scale, long dvp, long dvc,
                              const int* __restrict__ doc_end,
-                             char* smem_raw) {
+                             int n_blk, int grid_legacy, char* smem_raw) {
     unsigned short* lds = reinterpret_cast<unsigned short*>(smem_raw);
     float* lse_s = reinterpret_cast<float*>(smem_raw + O_STATS);
     float* delta_s = lse_s + TQ;
     const int lane = threadIdx.x & 63;
     const int wid = threadIdx.x >> 6;
     const int hi = lane >> 5, ln31 = lane & 31;
-    const int hkv = blockIdx.y, b = blockIdx.z;
+    // kv block 0 is seen by every q row: ascending order is heavy-first
+    const WgId wg = wg_decode<false>(n_blk, Hkv, B, grid_legacy);
+    const int hkv = wg.h, b = wg.b;
     const int rep = Hq / Hkv;
-    const int kvblk0 = blockIdx.x * WG_KV;  // heavy-first is natural here
+    const int kvblk0 = wg.blk * WG_KV;
     const int wv_kv0 = kvblk0 + wid * QBLK;
     const int kvg = wv_kv0 + ln31;          // this lane's kv row
     const float scale2k = scale * 1.44269504f;
@@ -1158,10 +1191,11 @@ template <int D, bool DOC = false>
 __global__ __launch_bounds__(NT, 2) void fwd2_kernel(
     const unsigned short* q, const unsigned short* k, const unsigned short* v,
     long vp, unsigned short* o, float* lse, int B, int Tq, int Tkv, int q_off,
-    int Hq, int Hkv, float scale, const int* doc_start) {
+    int Hq, int Hkv, float scale, const int* doc_start, int n_blk,
+    int grid_legacy) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   FwdV2<D, DOC>::run(q, k, v, vp, o, lse, B, Tq, Tkv, q_off, Hq, Hkv, scale,
-                     doc_start, smem_raw);
+                     doc_start, n_blk, grid_legacy, smem_raw);
 }
 
 template <int D, bool DOC = false>
@@ -1169,10 +1203,10 @@ __global__ __launch_bounds__(NT, 2) void dq2_kernel(
     const unsigned short* q, const unsigned short* k, const unsigned short* v,
     long vp, const unsigned short* dout, const float* lse, const float* delta,
     unsigned short* dq, int B, int Tq, int Tkv, int q_off, int Hq, int Hkv,
-    float scale, const int* doc_start) {
+    float scale, const int* doc_start, int n_blk, int grid_legacy) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   DQV2<D, DOC>::run(q, k, v, vp, dout, lse, delta, dq, B, Tq, Tkv, q_off, Hq,
-                    Hkv, scale, doc_start, smem_raw);
+                    Hkv, scale, doc_start, n_blk, grid_legacy, smem_raw);
 }
 
 template <int D, int MODE, bool DOC = false>
@@ -1182,11 +1216,12 @@ void dkdv2_kernel(
     const unsigned short* q, const unsigned short* k, const unsigned short* v,
     long vp, const unsigned short* dout, const float* lse, const float* delta,
     unsigned short* dk, unsigned short* dv, int B, int Tq, int Tkv, int q_off,
-    int Hq, int Hkv, float scale, long dvp, long dvc, const int* doc_end) {
+    int Hq, int Hkv, float scale, long dvp, long dvc, const int* doc_end,
+    int n_blk, int grid_legacy) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   DKDVV2<D, MODE, DOC>::run(q, k, v, vp, dout, lse, delta, dk, dv, B, Tq, Tkv,
-                            q_off, Hq, Hkv, scale, dvp, dvc, doc_end,
-                            smem_raw);
+                            q_off, Hq, Hkv, scale, dvp, dvc, doc_end, n_blk,
+                            grid_legacy, smem_raw);
 }
 
 // delta preprocess: delta[b,h,t] = rowsum(dO * O) (local copy — device
@@ -1264,6 +1299,21 @@ static void attn2_check_doc(const char* name, const torch::Tensor& t,
               " must be contiguous [B,T] matching q");
 }
 
+// MA_ATTN_GRID=legacy selects the dim3(n_blk, H, B) grid; anything else (or
+// unset) the linear globally heavy-first grid. Read on every call so one
+// process can flip it (A/B, tests).
+static bool attn2_grid_legacy() {
+  const char* e = getenv("MA_ATTN_GRID");
+  return e != nullptr && strcmp(e, "legacy") == 0;
+}
+
+static dim3 attn2_grid(int n_blk, int H, int B, bool legacy) {
+  if (legacy) return dim3(n_blk, H, B);
+  const long n = (long)n_blk * H * B;
+  TORCH_CHECK(n < (1L << 31), "attention grid too large: ", n, " workgroups");
+  return dim3((unsigned)n);
+}
+
 // ---------------------------------------------------------------------------
 static std::vector<torch::Tensor> attn_fwd2_impl(
     torch::Tensor q, torch::Tensor k, torch::Tensor v, bool causal,
@@ -1289,7 +1339,8 @@ static std::vector<torch::Tensor> attn_fwd2_impl(
   auto lse = torch::empty({B, Hq, Tq}, q.options().dtype(torch::kFloat32));
   const float scale = 1.0f / sqrtf((float)D);
   const int n_qblk = (Tq + attn2::QBLK * attn2::NW - 1) / (attn2::QBLK * attn2::NW);
-  dim3 grid(n_qblk, Hq, B);
+  const bool legacy = attn2_grid_legacy();
+  const dim3 grid = attn2_grid(n_qblk, Hq, B, legacy);
   auto stream = at::cuda::getCurrentHIPStream();
   auto launch = [&](auto kfn, size_t smem) {
     hipLaunchKernelGGL(kfn, grid, dim3(attn2::NT), smem, stream,
@@ -1297,7 +1348,8 @@ static std::vector<torch::Tensor> attn_fwd2_impl(
                        (const unsigned short*)k.data_ptr(),
                        (const unsigned short*)v.data_ptr(), vp,
                        (unsigned short*)o.data_ptr(), lse.data_ptr<float>(),
-                       B, Tq, Tkv, (int)q_offset, Hq, Hkv, scale, doc_start);
+                       B, Tq, Tkv, (int)q_offset, Hq, Hkv, scale, doc_start,
+                       n_qblk, (int)legacy);
   };
   if (doc_start != nullptr) {
     if (D == 128)
@@ -1416,29 +1468,32 @@ static std::vector<torch::Tensor> attn_bwd2_impl(
 
   const int WG = attn2::QBLK * attn2::NW;  // 256 q rows per dq workgroup
   const int n_qblk = (T + WG - 1) / WG;
+  const bool legacy = attn2_grid_legacy();
   auto launch_dq = [&](auto dqk, size_t smem_dq) {
-    hipLaunchKernelGGL(dqk, dim3(n_qblk, Hq, B), dim3(attn2::NT), smem_dq,
+    hipLaunchKernelGGL(dqk, attn2_grid(n_qblk, Hq, B, legacy),
+                       dim3(attn2::NT), smem_dq,
                        stream, (const unsigned short*)q.data_ptr(),
                        (const unsigned short*)k.data_ptr(),
                        (const unsigned short*)v.data_ptr(), vstride,
                        (const unsigned short*)dout.data_ptr(),
                        lse.data_ptr<float>(), delta.data_ptr<float>(),
                        (unsigned short*)dq.data_ptr(), B, T, Tkv, q_off, Hq,
-                       Hkv, scale, doc_start);
+                       Hkv, scale, doc_start, n_qblk, (int)legacy);
     HIP_CHECK_KERNEL();
   };
   auto launch_kv = [&](auto kfn, int wg_kv, int nthreads, size_t smem,
                        hipStream_t st) {
     const int n_kvblk = (Tkv + wg_kv - 1) / wg_kv;
-    hipLaunchKernelGGL(kfn, dim3(n_kvblk, Hkv, B), dim3(nthreads), smem,
-                       st, (const unsigned short*)q.data_ptr(),
+    hipLaunchKernelGGL(kfn, attn2_grid(n_kvblk, Hkv, B, legacy),
+                       dim3(nthreads), smem, st,
+                       (const unsigned short*)q.data_ptr(),
                        (const unsigned short*)k.data_ptr(),
                        (const unsigned short*)v.data_ptr(), vstride,
                        (const unsigned short*)dout.data_ptr(),
                        lse.data_ptr<float>(), delta.data_ptr<float>(),
                        (unsigned short*)dk.data_ptr(),
                        (unsigned short*)dv.data_ptr(), B, T, Tkv, q_off, Hq,
-                       Hkv, scale, dvp, dvc, doc_end);
+                       Hkv, scale, dvp, dvc, doc_end, n_kvblk, (int)legacy);
     HIP_CHECK_KERNEL();
   };
   bool used_side2 = false;

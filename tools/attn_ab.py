@@ -16,10 +16,15 @@ Layouts: `causal` (the causal kernels alone), `one` (a single document: the cost
 `uniform:L` (documents of L tokens), `mixed` (a fixed uneven list, different
 per batch row) or explicit starts `0,100,900`.  --ext loads another build of
 the extension (A/B across commits).
+
+Workgroup order:  python tools/attn_ab.py --grid-ab --rounds 5
+times the forward and the whole backward at the same shape under
+MA_ATTN_GRID=legacy and under the default linear grid, alternately.
 """
 
 import argparse
 import importlib.util
+import os
 import statistics
 import sys
 from pathlib import Path
@@ -166,6 +171,61 @@ def run_doc_layouts(ext, args, dev):
             print(f"  one-document {tag} bit-identical to causal: {same}")
 
 
+def set_grid(mode):
+    """MA_ATTN_GRID is read by the extension on every call."""
+    if mode == "legacy":
+        os.environ["MA_ATTN_GRID"] = "legacy"
+    else:
+        os.environ.pop("MA_ATTN_GRID", None)
+
+
+def run_grid_ab(ext, args, dev):
+    """Workgroup order A/B of the v2 kernels at the reference 2.7B shape:
+    the dim3(n_blk, H, B) grid (legacy) against the linear globally
+    heavy-first grid, alternating inside this process. Device events give
+    the forward and the whole backward (delta + dq || dkdv); for dq and dkdv
+    alone run this under `rocprofv3 --kernel-trace` and summarize the
+    database with tools/attn_grid_trace.py."""
+    B, T, H, D = 2, 4096, 32, 80
+    torch.manual_seed(0)
+    q = torch.randn(B, T, H, D, device=dev).bfloat16()
+    k = torch.randn(B, T, H, D, device=dev).bfloat16()
+    v = torch.randn(B, T, H, D, device=dev).bfloat16()
+    do = torch.randn(B, T, H, D, device=dev).bfloat16()
+    print(f"== grid order: B{B} T{T} H{H} D{D}, {args.rounds} rounds x "
+          f"{args.iters} iters, alternating")
+    modes = ("legacy", "linear")
+    times = {m: ([], []) for m in modes}
+    saved = {}
+    for _ in range(args.rounds):
+        for m in modes:
+            set_grid(m)
+            fwd = lambda: ext.attn_fwd_v2(q, k, v, True, 0)
+            o, lse = fwd()
+            bwd = lambda: ext.attn_bwd_v2(do, q, k, v, o, lse, True, 0)
+            saved.setdefault(m, (o, lse, *bwd()))
+            times[m][0].append(timeit(fwd, args.iters))
+            times[m][1].append(timeit(bwd, args.iters))
+    set_grid("linear")
+    for m in modes:
+        tf, tb = times[m]
+        print(f"  {m:>7}: fwd median {statistics.median(tf):7.3f} ms "
+              f"[{min(tf):.3f} .. {max(tf):.3f}]   bwd median "
+              f"{statistics.median(tb):7.3f} ms [{min(tb):.3f} .. {max(tb):.3f}]")
+        print("    rounds fwd: " + " ".join(f"{t:.3f}" for t in tf)
+              + " | bwd: " + " ".join(f"{t:.3f}" for t in tb))
+    for i, name in enumerate(("fwd", "bwd")):
+        leg, lin = times["legacy"][i], times["linear"][i]
+        gap = min(leg) - max(lin)
+        print(f"  {name}: legacy/linear median ratio "
+              f"{statistics.median(leg) / statistics.median(lin):.3f}; "
+              f"smallest legacy - largest linear = {gap:+.3f} ms; legacy "
+              f"spread {max(leg) - min(leg):.3f} ms")
+    for i, tag in enumerate(("o", "lse", "dq", "dk", "dv")):
+        same = torch.equal(saved["legacy"][i], saved["linear"][i])
+        print(f"  {tag} bit-identical between the grids: {same}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=50)
@@ -173,12 +233,19 @@ def main():
                     help="one | uniform:L | mixed | s0,s1,... (repeatable)")
     ap.add_argument("--rounds", type=int, default=5,
                     help="alternating measurement rounds per layout")
+    ap.add_argument("--grid-ab", action="store_true",
+                    help="legacy vs linear workgroup order (MA_ATTN_GRID) "
+                         "at the reference 2.7B shape")
     ap.add_argument("--ext", default=None,
                     help="path to another build of the op extension")
     args = ap.parse_args()
 
     ext = load_ext(args.ext)
     dev = "cuda"
+    if args.grid_ab:
+        run_grid_ab(ext, args, dev)
+        print("done")
+        return 0
     if args.doc_layout:
         run_doc_layouts(ext, args, dev)
         print("done")
